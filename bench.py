@@ -8,7 +8,14 @@ CRC kernel over the whole batch (every block checksummed, results written to HBM
 (global block ids rank*1M ...): weak scaling, no collective on the data path; the only collectives
 are the timing barrier and the max-over-ranks reduction.
 
-Prints one JSON line (rank 0). Extra fields: roofline (dominant kernel: algorithmic bytes per
+A plain run sets up, warms up, times the --steps steps and prints one JSON line (rank 0) with the
+headline figure (`value`, `ms_per_step`) and what describes the run; nothing else is measured or
+checked. --dump-outputs DIR also writes the CRCs the last timed step left in HBM (what a caller of
+the batch entry point receives) as DIR/crc32.npy (float64, one value per block, exact for 32-bit CRCs;
+DIR/crc32_rank<r>.npy per rank with --gpus N > 1); the synthetic inputs are the same in every run.
+
+--full adds the extra fields, each measured or checked after the timed steps (the --no-* options
+drop single ones): build (library id against the tree), roofline (dominant kernel: algorithmic bytes per
 launch / HIP-event launch time vs 8 TB/s HBM peak), cpu_baseline (the reference's own crc32.cpp
 compiled from /root/reference into oracle/_ref, or the oracle port, on host cores over the same
 buffers; plus a slicing-by-8 row that is not the reference), bit_exact (this run's CRCs vs the
@@ -570,6 +577,12 @@ def main():
     ap.add_argument("--min-warmup-ms", type=float, default=1000.0,
                     help="keep warming up (untimed) until this much wall time has passed (clock ramp)")
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement and check (bit_exact, roofline, "
+                         "cpu_baseline, pipelined_two_streams, e2e_host, more_configs, wal_payload_batches, "
+                         "bit_exact_paths, build); the --no-* options below drop single ones")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the CRCs of the last timed step to DIR/crc32.npy (float64, one per block)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="cfg3: skip the host-memory end-to-end measurement")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the two-stream pipelined rate (extra field)")
@@ -582,6 +595,9 @@ def main():
     ap.add_argument("--traffic-csv", default=None,
                     help="rocprofv3 --pmc counter_collection.csv (FETCH_SIZE) of this command, for roofline.traffic")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps and the line, none of the extra measurements and checks
+        args.no_cpu_baseline = args.no_e2e = args.no_pipelined = args.no_more_configs = True
+        args.no_paths = args.no_wal_payloads = True
 
     import torch
     import torch.distributed as dist
@@ -634,13 +650,21 @@ def main():
 
     # correctness of this exact buffer, from the last timed step (checked after the timed region so
     # no CPU pause lets the clocks fall between warmup and timing)
-    crcs = out.cpu().numpy().view(np.uint32).copy()
-    bit_exact, full = verify_rank(ora, args.config, first, crcs, blen, None if blen else lens)
+    crcs = out.cpu().numpy().view(np.uint32).copy() if args.full or args.dump_outputs else None
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "crc32.npy" if world == 1 else f"crc32_rank{rank}.npy"
+        np.save(os.path.join(args.dump_outputs, name), crcs.astype(np.float64))
+    bit_exact, full = verify_rank(ora, args.config, first, crcs, blen, None if blen else lens) if args.full \
+        else (None, False)
     ranks_seen = 1
     if use_dist:
-        elapsed, kernel_ms, bit_exact, ranks_seen, full = reduce_timing(
-            elapsed, kernel_ms, bit_exact, dist, dev if backend == "nccl" else None, full)
-    if full:
+        elapsed, kernel_ms, all_exact, ranks_seen, full = reduce_timing(
+            elapsed, kernel_ms, bit_exact is not False, dist, dev if backend == "nccl" else None, full)
+        bit_exact = all_exact if args.full else None
+    if not args.full:
+        scope = "not checked (a plain run; --full checks every block)"
+    elif full:
         scope = f"every block of every rank's shard (golden XOR/SUM32 of blocks [r*{nblocks}, (r+1)*{nblocks})) " \
                 "and its first 64 blocks against the oracle"
     else:
@@ -657,6 +681,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "warmup_run": {"steps": warm_steps, "ms": round(warm_ms, 1), "min_ms": args.min_warmup_ms,
                        "note": "untimed; at least --warmup steps, continued until min_ms of wall time (clock ramp)"},
         "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
@@ -670,9 +695,9 @@ def main():
         "bit_exact": bit_exact,
         "bit_exact_scope": scope,
         "ranks_seen": ranks_seen,
-        "roofline": roofline(bytes_per_step, kernel_ms, args.config, args.traffic_csv),
+        "roofline": roofline(bytes_per_step, kernel_ms, args.config, args.traffic_csv) if args.full else None,
         "cpu_baseline": None,
-        "build": build_identity(),
+        "build": build_identity() if args.full else None,
     }
     if world == 1 and not args.no_pipelined:
         # A caller checksumming a stream of batches may alternate two HIP streams: each launch's

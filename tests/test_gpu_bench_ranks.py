@@ -30,12 +30,42 @@ def run_bench(nproc, extra_env, config="cfg2", more=False):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", str(nproc), "--config", config, "--steps", "3", "--warmup", "1", "--min-warmup-ms", "0",
-           "--no-cpu-baseline", "--no-pipelined", "--no-e2e"] + ([] if more else ["--no-more-configs"])
+           "--full", "--no-cpu-baseline", "--no-pipelined", "--no-e2e"] + ([] if more else ["--no-more-configs"])
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]  # rank 0 prints the one line
     return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_crcs(gpu, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and measures or checks nothing else; with
+    --dump-outputs it writes the last timed step's CRCs, one float64 per block, and those are the
+    committed golden aggregates of cfg2's blocks [0, 1 M)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--min-warmup-ms", "0", "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["full"] is False
+    assert line["unit"] == "GiB/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    # value is the bytes of the 2 timed steps over their wall time, ms_per_step that time per step
+    nblocks, blen, _ = bench.CONFIGS["cfg2"]
+    assert line["value"] == pytest.approx(nblocks * blen / (1 << 30) / (line["ms_per_step"] * 1e-3), rel=1e-3)
+    for extra in ("pipelined_two_streams", "more_configs", "wal_payload_batches", "bit_exact_paths", "e2e_host"):
+        assert extra not in line, extra
+    assert line["cpu_baseline"] is None and line["roofline"] is None and line["bit_exact"] is None
+    assert [p.name for p in tmp_path.iterdir()] == ["crc32.npy"]
+    crcs = np.load(tmp_path / "crc32.npy")
+    assert crcs.dtype == np.float64 and crcs.shape == (nblocks,)
+    assert bench.check_shard(crcs.astype(np.uint32), bench.shard_golden("cfg2", 0, nblocks))
 
 
 @pytest.mark.gpu

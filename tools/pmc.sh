@@ -13,5 +13,5 @@ for group in \
   "WRITE_SIZE" \
   "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $group -d "$OUT/p$i" -o pmc --output-format csv -- python3 bench.py --no-cpu-baseline "$@" > "$OUT/p$i.log" 2>&1
+  timeout -k 10 300 rocprofv3 --pmc $group -d "$OUT/p$i" -o pmc --output-format csv -- python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/p$i.log" 2>&1
 done
