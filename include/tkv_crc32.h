@@ -155,6 +155,27 @@ int tkv_wal_verify_device(const uint8_t *d_wal, uint64_t size, uint64_t *n_good,
 int tkv_wal_check_records_device(const uint8_t *d_img, uint64_t size, const uint32_t *d_rec_off, uint64_t n,
                                  uint32_t max_payload, uint32_t *d_crc, uint64_t *d_first_bad, void *stream);
 
+/* Verify the image as tkv_wal_verify_device does and also list its good records: what the recovery
+ * loop of engine::create needs besides the verdict (engine.cpp:31-53: every good record goes to the
+ * memtable, and the next sequence number is the largest one seen plus 1).
+ * d_off64 / d_off32 (device, either or both may be NULL): start offset of good record i, in chain
+ * order, for i < min(*n_good, cap). Entries at and after that index are not written. cap > 0 with both
+ * NULL, and d_off32 with size > 4 GiB, are TKV_INVALID_ARGUMENT. *n_good is the full count also when
+ * cap is smaller; cap == 0 is a verify that additionally returns *max_sequence.
+ * *max_sequence: the largest sequence_ field (u64 LE at record byte 9) over the good records,
+ * 0 when there are none (engine.cpp:17,46).
+ * Status, *n_good, *stop_offset: identical to tkv_wal_verify_device on the same image. The chain the
+ * verify settled is scanned (per-region record counts) and the image read once more to write the
+ * offsets out; d_off32 is the list tkv_wal_check_records_device takes. Synchronous on `stream`. */
+int tkv_wal_index_device(const uint8_t *d_wal, uint64_t size, uint64_t *d_off64, uint32_t *d_off32, uint64_t cap,
+                         uint64_t *n_good, uint64_t *stop_offset, uint64_t *max_sequence, void *stream);
+
+/* Host image (pageable or pinned): copied to the device as tkv_wal_verify does, indexed there, the
+ * offsets of the first min(*n_good, cap) good records copied back to h_off64 (cap entries; may be NULL
+ * when cap is 0). */
+int tkv_wal_index(const uint8_t *h_wal, uint64_t size, uint64_t *h_off64, uint64_t cap, uint64_t *n_good,
+                  uint64_t *stop_offset, uint64_t *max_sequence);
+
 /* Stamp n records in place (host memory): for record i at h_buf + h_offsets[i] of total size
  * h_sizes[i] (>= 8), write crc32 of bytes [8, size) LE at offset 4 (wal.cpp:54-58). */
 int tkv_wal_stamp(uint8_t *h_buf, const uint64_t *h_offsets, const uint32_t *h_sizes, uint64_t n);
@@ -279,6 +300,9 @@ void tkv_debug_wal_last(uint64_t out[4]);
  * task may walk), the most regions one task walked and all regions walked. Writes up to n words;
  * returns the number available (0 when the sweep needed no fix-up). */
 size_t tkv_debug_wal_rounds(uint64_t *out, size_t n);
+/* Fix-up rounds a device WAL verify or index may take before it hands the image to the exact host walk
+ * (default 256; 0 restores it). Returns the previous value. Tests set 1 to reach the hand-over. */
+uint64_t tkv_debug_set_wal_round_budget(uint64_t rounds);
 /* Which path the last irregular batch on `stream` took: 1 = byte-stream row walk (blocks back to
  * back, each at least 64 bytes), 0 = general row walk; -1 on error. Synchronizes
  * the stream. */

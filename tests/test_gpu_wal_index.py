@@ -1,0 +1,461 @@
+"""Device WAL record index (tkv_wal_index_device / tkv_wal_index): the start offsets of the good
+records in chain order and the largest sequence_ among them, next to the verify's verdict.
+
+Every case is compared with a sequential decode written here (the record_len chain, CRCs from the test
+oracle, the key/value bounds: wal.cpp:63-121, as sequential_decode in test_gpu_wal_device.py), extended to
+return the good records' starts and their largest sequence_. Sequence numbers are random, so the
+maximum is not the last record's. Every offsets buffer is filled with a sentinel and is a few entries
+longer than `cap`, so an entry written at or past min(n_good, cap) shows. Every clean image ends
+with a short record.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import tinykvpp_amd as tk
+
+pytestmark = pytest.mark.gpu
+
+REGION = 7168      # kRegion: image bytes per region of the sweep and of the index
+SCAN_BLOCK = 256   # kScanThreads: regions per workgroup of the index's count/base scan kernels
+SENT64 = -0x0123456789ABCDEF
+SENT32 = -0x01234567
+PAD = 5
+U64 = ctypes.c_uint64
+VP = ctypes.c_void_p
+
+
+# ---- images ---------------------------------------------------------------------------------------
+
+def stamp(img, offs, sizes):
+    offs = np.ascontiguousarray(offs, np.uint64)
+    sizes = np.ascontiguousarray(sizes, np.uint32)
+    tk.check(tk.load_library().tkv_wal_stamp(VP(img.ctypes.data), VP(offs.ctypes.data), VP(sizes.ctypes.data), offs.size))
+
+
+def make_image(rng, klen, vlen, fake=False):
+    """Stamped image of records laid out as wal.cpp:19-61 with random sequence numbers. fake: every
+    value is a run of well-formed 40-byte records (plausible headers off the chain)."""
+    klen, vlen = klen.astype(np.uint64), vlen.astype(np.uint64)
+    n = klen.size
+    size = 26 + klen + vlen
+    offs = np.zeros(n, np.uint64)
+    offs[1:] = np.cumsum(size[:-1])
+    img = rng.integers(0, 256, int(size.sum()), dtype=np.uint8)
+    hdr = np.zeros((n, 26), np.uint8)
+    hdr[:, 0:4] = (size - 8).astype("<u4").view(np.uint8).reshape(-1, 4)
+    hdr[:, 9:17] = rng.integers(0, 1 << 62, n).astype("<u8").view(np.uint8).reshape(-1, 8)
+    hdr[:, 18:22] = klen.astype("<u4").view(np.uint8).reshape(-1, 4)
+    hdr[:, 22:26] = vlen.astype("<u4").view(np.uint8).reshape(-1, 4)
+    img[offs.astype(np.int64)[:, None] + np.arange(26)] = hdr
+    if fake:
+        f = np.zeros(40, np.uint8)
+        f[0:4] = np.frombuffer((32).to_bytes(4, "little"), np.uint8)
+        f[18:22] = np.frombuffer((6).to_bytes(4, "little"), np.uint8)
+        f[22:26] = np.frombuffer((8).to_bytes(4, "little"), np.uint8)
+        for i in range(n):
+            v0, reps = int(offs[i] + 26 + klen[i]), int(vlen[i]) // 40
+            if reps:
+                img[v0:v0 + 40 * reps] = np.tile(f, reps)
+    stamp(img, offs, size)
+    return img, offs, size
+
+
+def short_image(rng, n_rec, vmax=64):
+    """Records of 26 to 26 + 23 + vmax bytes."""
+    return make_image(rng, rng.integers(0, 24, n_rec), rng.integers(0, vmax + 1, n_rec))
+
+
+def record(rng, plen, klen=4):
+    """One unstamped record with record_len = plen >= 18 (random sequence number)."""
+    klen = min(klen, plen - 18)
+    vlen = plen - 18 - klen
+    body = bytearray(rng.integers(0, 256, 8 + plen, dtype=np.uint8).tobytes())
+    body[0:4] = plen.to_bytes(4, "little")
+    body[4:8] = b"\0\0\0\0"
+    body[8] = 0
+    body[16] &= 0x3F  # sequence numbers below 2^62
+    body[17] = 0
+    body[18:22] = klen.to_bytes(4, "little")
+    body[22:26] = vlen.to_bytes(4, "little")
+    return bytes(body)
+
+
+def join(recs):
+    img = np.frombuffer(b"".join(recs), np.uint8).copy()
+    sizes = np.array([len(r) for r in recs], np.uint64)
+    offs = np.zeros(len(recs), np.uint64)
+    offs[1:] = np.cumsum(sizes[:-1])
+    stamp(img, offs, sizes)
+    return img, offs, sizes
+
+
+# ---- the expected index ---------------------------------------------------------------------------
+
+def decode(oracle, img, size):
+    """wal_entry::decode record after record (engine.cpp:31-53): (status, n_good, stop_offset), the
+    good records' starts (uint64) and their largest sequence_ (0 for none)."""
+    img = np.ascontiguousarray(img[:size])
+    b = img.tobytes()
+    starts, p, broke = [], 0, False
+    while p < size:
+        if size - p < 26:
+            broke = True
+            break
+        rlen = int.from_bytes(b[p:p + 4], "little")
+        if rlen + 8 > size - p:
+            broke = True
+            break
+        starts.append(p)
+        p += 8 + rlen
+    r = np.array(starts, np.uint64)
+    status, n_good, stop = ("corrupted" if broke else "ok"), len(starts), p
+    if starts:
+        at = r.astype(np.int64)
+        field = lambda o, w, t: img[at[:, None] + o + np.arange(w)].copy().view(t).reshape(-1)  # noqa: E731
+        rl, stored = field(0, 4, "<u4"), field(4, 4, "<u4")
+        kl, vl = field(18, 4, "<u4").astype(np.uint64), field(22, 4, "<u4").astype(np.uint64)
+        got = oracle.batch(img, r + 8, rl)
+        bad = np.flatnonzero((got != stored) | (26 + kl + vl > 8 + rl.astype(np.uint64)))
+        if bad.size:
+            status, n_good, stop = "corrupted", int(bad[0]), int(r[bad[0]])
+        seq = field(9, 8, "<u8")[:n_good]
+    mseq = int(seq.max()) if starts and n_good else 0
+    return (status, n_good, stop), r[:n_good], mseq
+
+
+def wal_last():
+    out = (U64 * 4)()
+    tk.load_library().tkv_debug_wal_last(out)
+    return {"passes": out[0], "host_walk": out[1], "copied": out[2], "fast": out[3]}
+
+
+def to_device(img, size, shift=0):
+    d = torch.zeros(size + shift, dtype=torch.uint8, device="cuda")
+    if size:
+        d[shift:] = torch.from_numpy(np.ascontiguousarray(img[:size])).cuda()
+    return d[shift:]
+
+
+def index_raw(view, size, cap, use64=True, use32=True):
+    """tkv_wal_index_device on a device image with sentinel-filled offsets buffers of cap + PAD
+    entries: ((status, n_good, stop), offsets64, offsets32 (numpy, whole buffers), max_sequence)."""
+    o64 = torch.full((cap + PAD,), SENT64, dtype=torch.int64, device="cuda")
+    o32 = torch.full((cap + PAD,), SENT32, dtype=torch.int32, device="cuda")
+    good, stop, seq = U64(0), U64(0), U64(0)
+    rc = tk.load_library().tkv_wal_index_device(
+        VP(view.data_ptr()) if size else None, size, VP(o64.data_ptr()) if use64 else None,
+        VP(o32.data_ptr()) if use32 else None, cap, ctypes.byref(good), ctypes.byref(stop), ctypes.byref(seq),
+        VP(torch.cuda.current_stream().cuda_stream))
+    assert rc in (0, 4), (rc, tk.load_library().tkv_last_error())
+    torch.cuda.synchronize()
+    return (("ok" if rc == 0 else "corrupted"), good.value, stop.value), o64.cpu().numpy(), o32.cpu().numpy(), seq.value
+
+
+def check(oracle, img, size, shift=0, cap=None):
+    """One image through tkv_wal_verify_device and tkv_wal_index_device (both widths at once) against the
+    sequential decode; returns the decode's verdict."""
+    want, starts, mseq = decode(oracle, img, size)
+    view = to_device(img, size, shift)
+    verdict = tk.wal.verify_device(view, size)
+    cap = size // 26 if cap is None else cap
+    got, o64, o32, seq = index_raw(view, size, cap)
+    assert got == verdict == want
+    k = min(want[1], cap)
+    assert np.array_equal(o64[:k].view(np.uint64), starts[:k])
+    assert np.array_equal(o32[:k].view(np.uint32), starts[:k].astype(np.uint32))
+    assert (o64[k:] == SENT64).all() and (o32[k:] == SENT32).all(), "an entry at or past min(n_good, cap) was written"
+    assert seq == mseq
+    return want
+
+
+# ---- 1. tiny and truncated images -----------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def tiny_image(gpu):
+    return short_image(np.random.default_rng(9), 400, vmax=200)
+
+
+@pytest.mark.parametrize("n", [0, 1, 25, 26, 27, 33, 34, 35, 255, 256, 257, 2047, 2048, 2049, 4096 + 17, 16383, 16384,
+                               16385, 16384 + 1024 + 5])
+def test_tiny_and_truncated_images(gpu, oracle, tiny_image, n):
+    """A short-record WAL cut to n bytes (the sizes of test_tiny_and_piece_boundary_images): torn tails,
+    a single region, piece and region boundaries."""
+    img, offs, size = tiny_image
+    assert img.size > 16384 + 1024 + 5
+    want = check(oracle, img, n)
+    if n >= int(size[0]):
+        assert want[1] >= 1
+
+
+# ---- 2. region ends -------------------------------------------------------------------------------
+
+def region_end_image(rng, tail=()):
+    """Short records with: a record ending exactly at byte 7168, one starting at byte 7167 of a
+    region, one whose header straddles a region end, and records with record_len 18 (empty key and
+    value), 240, 241, 3000, 7168, 20000, 65536, 65537, 100000 (regions without a record start, the
+    giant hop). Ends with `tail` and a short record. Returns (img, offs, sizes, marks)."""
+    recs, pos, marks = [], 0, {}
+
+    def add(r):
+        nonlocal pos
+        recs.append(r)
+        pos += len(r)
+
+    def pad_to(t):
+        while t - pos > 200:
+            add(record(rng, int(rng.integers(18, 83))))
+        add(record(rng, t - pos - 8))  # 26..200 bytes, ends exactly at t
+        assert pos == t
+
+    pad_to(REGION)
+    marks["ends_at_region_end"] = len(recs) - 1
+    pad_to(3 * REGION - 1)
+    marks["starts_at_7167"] = len(recs)
+    add(record(rng, 40))
+    pad_to(5 * REGION - 10)
+    marks["header_straddles"] = len(recs)
+    add(record(rng, 60))
+    for plen in (18, 240, 241, 3000, 7168, 20000, 65536, 65537, 100000):
+        for _ in range(int(rng.integers(3, 40))):
+            add(record(rng, int(rng.integers(18, 83))))
+        marks[plen] = len(recs)
+        add(record(rng, plen))
+    for _ in range(30):
+        add(record(rng, int(rng.integers(18, 83))))
+    for r in tail:
+        add(r)
+    add(record(rng, 50))
+    img, offs, sizes = join(recs)
+    return img, offs, sizes, marks
+
+
+def test_region_ends(gpu, oracle):
+    rng = np.random.default_rng(21)
+    img, offs, sizes, marks = region_end_image(rng)
+    assert int(offs[marks["ends_at_region_end"]] + sizes[marks["ends_at_region_end"]]) == REGION
+    assert int(offs[marks["starts_at_7167"]]) % REGION == REGION - 1
+    s = int(offs[marks["header_straddles"]])
+    assert s // REGION != (s + 25) // REGION
+    regions_with_start = set((offs // REGION).astype(np.int64).tolist())
+    assert len(regions_with_start) < (img.size + REGION - 1) // REGION  # some region has no record start
+    want = check(oracle, img, img.size)
+    assert want == ("ok", offs.size, img.size)
+    # a payload length of 0 (record_len = 0: key and value cannot fit, wal.cpp:118-121) is a bad record
+    # with good records behind it: everything in front of it is listed, nothing after
+    tiny = (0).to_bytes(4, "little") + b"\0\0\0\0"
+    img2, offs2, _, _ = region_end_image(np.random.default_rng(21), tail=(tiny,))
+    want = check(oracle, img2, img2.size)
+    assert want == ("corrupted", offs2.size - 2, int(offs2[-2]))
+
+
+# ---- 3. corruption, 4. small cap, 5. misaligned base ------------------------------------------------
+
+@pytest.fixture(scope="module")
+def ten_regions(gpu):
+    """About 1200 short records over ten regions."""
+    rng = np.random.default_rng(33)
+    img, offs, size = short_image(rng, 1200)
+    assert img.size > 9 * REGION
+    return img, offs, size
+
+
+def second_region_record(offs):
+    return int(np.searchsorted(offs, REGION + 100))
+
+
+def test_corruption(gpu, oracle, ten_regions):
+    img, offs, size = ten_regions
+    img = img.copy()
+    n = offs.size
+    for bad in (0, 1, second_region_record(offs), n // 2, n - 1):  # a payload byte flipped
+        o = int(offs[bad] + size[bad]) - 1
+        img[o] ^= 0x04
+        assert check(oracle, img, img.size) == ("corrupted", bad, int(offs[bad]))
+        img[o] ^= 0x04
+    # a record_len in the middle that overruns the image: the chain breaks there
+    bad = n // 2 + 7
+    o = int(offs[bad])
+    old = img[o:o + 4].copy()
+    img[o:o + 4] = np.frombuffer((0xFFFFFF00).to_bytes(4, "little"), np.uint8)
+    assert check(oracle, img, img.size) == ("corrupted", bad, o)
+    img[o:o + 4] = old
+    # key/value bounds: key_len grown past the record, the record stamped again so that only
+    # wal.cpp:118-121 fails
+    bad = n // 3
+    o = int(offs[bad])
+    old = img[o:o + int(size[bad])].copy()
+    img[o + 18:o + 22] = np.frombuffer((int(size[bad]) + 1).to_bytes(4, "little"), np.uint8)
+    stamp(img, offs[bad:bad + 1], size[bad:bad + 1])
+    assert oracle.crc(img[o + 8:o + int(size[bad])].tobytes()) == int.from_bytes(img[o + 4:o + 8].tobytes(), "little")
+    assert check(oracle, img, img.size) == ("corrupted", bad, o)
+    img[o:o + int(size[bad])] = old
+    assert check(oracle, img, img.size) == ("ok", n, img.size)
+
+
+def test_small_cap(gpu, oracle, ten_regions):
+    img, offs, size = ten_regions
+    n = offs.size
+    for cap in (0, 1, n - 1, n):
+        assert check(oracle, img, img.size, cap=cap) == ("ok", n, img.size)
+    # cap == 0 with no offsets arrays: a verify that also returns max_sequence
+    view = to_device(img, img.size)
+    got, o64, o32, seq = index_raw(view, img.size, 0, use64=False, use32=False)
+    assert got == ("ok", n, img.size) and seq == decode(oracle, img, img.size)[2]
+    # a corrupted image and a cap below its good prefix
+    img = img.copy()
+    bad = n // 2
+    img[int(offs[bad]) + 30] ^= 0x80
+    for cap in (0, 1, bad - 1, bad, bad + 3):
+        assert check(oracle, img, img.size, cap=cap) == ("corrupted", bad, int(offs[bad]))
+
+
+@pytest.mark.parametrize("shift", [3])
+def test_misaligned_base(gpu, oracle, ten_regions, shift):
+    """The image at byte offset 3 of its allocation (the window's first bytes lie in front of it)."""
+    img, offs, size = ten_regions
+    n = offs.size
+    assert check(oracle, img, img.size, shift=shift) == ("ok", n, img.size)
+    assert check(oracle, img, img.size - 11, shift=shift)[0] == "corrupted"  # torn tail
+    img = img.copy()
+    bad = second_region_record(offs) + 5
+    img[int(offs[bad]) + 27] ^= 0x01
+    assert check(oracle, img, img.size, shift=shift) == ("corrupted", bad, int(offs[bad]))
+
+
+# ---- 6. fake headers --------------------------------------------------------------------------------
+
+def test_values_made_of_records(gpu, oracle):
+    """Every value a run of well-formed records, a few hundred KiB: region entries settle in fix-up
+    rounds (more than one device round, or the case shows nothing), and the index follows the
+    settled chain, not the fake ones."""
+    rng = np.random.default_rng(12)
+    n = 160
+    klen, vlen = rng.integers(0, 40, n), rng.integers(400, 4000, n)
+    klen[-1], vlen[-1] = 8, 40  # ends with a short record
+    img, offs, size = make_image(rng, klen, vlen, fake=True)
+    assert 200 << 10 < img.size < 600 << 10
+    assert check(oracle, img, img.size) == ("ok", n, img.size)
+    last = wal_last()  # of the index call, the last one check() made
+    assert last["passes"] > 1 and last["host_walk"] == 0, last
+    img[int(offs[n - 20]) + 30] ^= 0x40
+    assert check(oracle, img, img.size) == ("corrupted", n - 20, int(offs[n - 20]))
+
+
+def test_host_walk_hand_over(gpu, oracle):
+    """With a fix-up budget of one round (tkv_debug_set_wal_round_budget) the values-made-of-records
+    image goes to the exact host walk: tkv_wal_index_device copies that walk's positions to both
+    device arrays (u64 and the narrowed u32), tkv_wal_index to the host array; same results."""
+    rng = np.random.default_rng(12)
+    n = 160
+    klen, vlen = rng.integers(0, 40, n), rng.integers(400, 4000, n)
+    klen[-1], vlen[-1] = 8, 40
+    img, offs, size = make_image(rng, klen, vlen, fake=True)
+    lib = tk.load_library()
+    prev = lib.tkv_debug_set_wal_round_budget(1)
+    try:
+        for flip in (None, n - 20):
+            if flip is not None:
+                img[int(offs[flip]) + 30] ^= 0x40
+            want = check(oracle, img, img.size)
+            assert wal_last()["host_walk"] == 1
+            assert want == (("ok", n, img.size) if flip is None else ("corrupted", flip, int(offs[flip])))
+            assert check(oracle, img, img.size, cap=7) == want  # fewer entries than records
+            assert wal_last()["host_walk"] == 1
+            status, o, stop, seq = tk.wal.index(img.tobytes())
+            assert wal_last()["host_walk"] == 1
+            _, starts, mseq = decode(oracle, img, img.size)
+            assert (status, o.size, stop) == want and seq == mseq and np.array_equal(o, starts)
+    finally:
+        lib.tkv_debug_set_wal_round_budget(prev)
+
+
+# ---- 7. many regions, 8. stale scratch ----------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def many_regions(gpu):
+    """About 4 MiB of 26-90 byte records: 586 regions, three workgroups of the region scan
+    (SCAN_BLOCK = 256 regions each)."""
+    rng = np.random.default_rng(44)
+    img, offs, size = short_image(rng, 72_000, vmax=41)
+    assert int(size.min()) >= 26 and int(size.max()) <= 90
+    assert (img.size + REGION - 1) // REGION > 2 * SCAN_BLOCK
+    return img, offs, size
+
+
+def test_many_regions(gpu, oracle, many_regions):
+    img, offs, size = many_regions
+    assert check(oracle, img, img.size) == ("ok", offs.size, img.size)
+    img = img.copy()
+    bad = int(np.searchsorted(offs, 2 * SCAN_BLOCK * REGION + 5000))  # in the scan's third workgroup
+    img[int(offs[bad]) + 26] ^= 0x20
+    assert check(oracle, img, img.size) == ("corrupted", bad, int(offs[bad]))
+
+
+def test_stale_scratch(gpu, oracle, many_regions, ten_regions):
+    """A larger image, then a smaller different one on the same device: the second result owes
+    nothing to the region arrays, bases and result words the first left in the scratch."""
+    big = many_regions[0]
+    assert check(oracle, big, big.size)[0] == "ok"
+    img, offs, size = ten_regions
+    img = img.copy()
+    bad = offs.size - 40
+    img[int(offs[bad]) + 29] ^= 0x02
+    assert check(oracle, img, img.size) == ("corrupted", bad, int(offs[bad]))
+    assert check(oracle, img, int(offs[5])) == ("ok", 5, int(offs[5]))
+
+
+# ---- 9. both widths and the round trip, 10. host entry -------------------------------------------------
+
+def test_widths_and_round_trip(gpu, oracle, ten_regions):
+    img, offs, size = ten_regions
+    n = offs.size
+    view = to_device(img, img.size)
+    s64, o64, stop64, q64 = tk.wal.index_device(view)
+    s32, o32, stop32, q32 = tk.wal.index_device(view, offsets32=True)
+    assert (s64, stop64, q64) == (s32, stop32, q32) == ("ok", img.size, decode(oracle, img, img.size)[2])
+    assert o64.dtype == torch.int64 and o32.dtype == torch.int32 and o64.numel() == o32.numel() == n
+    assert np.array_equal(o64.cpu().numpy().view(np.uint64), offs)
+    assert torch.equal(o64, o32.to(torch.int64))
+    first_bad, _ = tk.wal.check_records_device(view, o32, max_payload=128)
+    assert int(first_bad.item()) == n
+    # corrupted: the good prefix plus the stop offset; exactly the record at index n_good fails
+    img = img.copy()
+    bad = n // 2 + 3
+    img[int(offs[bad]) + 40] ^= 0x08
+    view = to_device(img, img.size)
+    out = torch.full((n + 1,), SENT32, dtype=torch.int32, device="cuda")
+    status, o32, stop, _ = tk.wal.index_device(view, out=out, offsets32=True)
+    assert (status, o32.numel(), stop) == ("corrupted", bad, int(offs[bad]))
+    assert (out[bad:] == SENT32).all()
+    out[bad] = stop
+    first_bad, _ = tk.wal.check_records_device(view, out[:bad + 1], max_payload=128)
+    assert int(first_bad.item()) == bad
+    with pytest.raises(ValueError):  # an `out` shorter than the good prefix
+        tk.wal.index_device(view, out=torch.empty(bad - 1, dtype=torch.int64, device="cuda"))
+
+
+def test_host_entry(gpu, oracle, ten_regions, many_regions):
+    """wal.index on a pageable host image equals wal.index_device (and the sequential decode)."""
+    for img, offs, size in (ten_regions, many_regions):
+        for cut, flip in ((img.size, None), (img.size - 7, None), (img.size, offs.size // 2)):
+            im = img.copy()
+            if flip is not None:
+                im[int(offs[flip]) + 28] ^= 0x10
+            want, starts, mseq = decode(oracle, im, cut)
+            status, o, stop, seq = tk.wal.index(im[:cut].tobytes())
+            assert wal_last()["copied"] == 1
+            assert (status, o.size, stop) == want and seq == mseq
+            assert o.dtype == np.uint64 and np.array_equal(o, starts)
+            ds, do, dstop, dseq = tk.wal.index_device(to_device(im, cut))
+            assert (ds, dstop, dseq) == (status, stop, seq)
+            assert np.array_equal(do.cpu().numpy().view(np.uint64), o)
+    # the C call with a cap below the count: the full count, nothing written at or past cap
+    img, offs, size = ten_regions
+    buf = np.full(10 + PAD, 0xAAAAAAAAAAAAAAAA, np.uint64)
+    good, stop, seq = U64(0), U64(0), U64(0)
+    assert tk.load_library().tkv_wal_index(VP(img.ctypes.data), img.size, VP(buf.ctypes.data), 10, ctypes.byref(good),
+                                           ctypes.byref(stop), ctypes.byref(seq)) == 0
+    assert good.value == offs.size and np.array_equal(buf[:10], offs[:10]) and (buf[10:] == 0xAAAAAAAAAAAAAAAA).all()

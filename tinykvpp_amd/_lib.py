@@ -50,6 +50,10 @@ SIGNATURES = {
     "tkv_crc32_combine": (_u32, [_u32, _u32, _u64]),
     "tkv_wal_verify": (_int, [_u8p, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "tkv_wal_verify_device": (_int, [_u8p, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _vp]),
+    "tkv_wal_index_device": (_int, [_u8p, _u64, _vp, _vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                                    ctypes.POINTER(_u64), _vp]),
+    "tkv_wal_index": (_int, [_u8p, _u64, _vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                             ctypes.POINTER(_u64)]),
     "tkv_wal_stamp": (_int, [_u8p, _vp, _vp, _u64]),
     "tkv_wal_check_records_device": (_int, [_u8p, _u64, _vp, _u64, _u32, _vp, _vp, _vp]),
     "tkv_fill_synthetic_uniform": (_int, [_u8p, _u64, _u64, _u64, _u64, _u64, _vp]),
@@ -76,6 +80,7 @@ SIGNATURES = {
     "tkv_debug_wal_chain": (_sz, [_u8p, _u64, _vp, _sz, ctypes.POINTER(_u64), ctypes.POINTER(_int)]),
     "tkv_debug_wal_last": (None, [_vp]),
     "tkv_debug_wal_rounds": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
+    "tkv_debug_set_wal_round_budget": (_u64, [_u64]),
     "tkv_debug_update_counts": (None, [_vp]),
     "tkv_debug_update_counts_n": (_sz, [_vp, _sz]),
     "tkv_debug_irregular_mode": (_int, [_vp]),
@@ -88,7 +93,7 @@ SIGNATURES = {
 }
 
 # symbols an older build may lack (tools/ab_lib.py loads earlier builds for A/B runs)
-OPTIONAL = {"tkv_build_id"}
+OPTIONAL = {"tkv_build_id", "tkv_wal_index_device", "tkv_wal_index", "tkv_debug_set_wal_round_budget"}
 
 _lib = None
 

@@ -198,7 +198,19 @@ Chain wal_chain(const std::uint8_t* w, std::uint64_t size, std::uint64_t start, 
 
 Chain wal_chain(const std::uint8_t* w, std::uint64_t size) { return wal_chain(w, size, 0, size); }
 
-int wal_verify_host_walk(const uint8_t* h_wal, uint64_t size, uint64_t* n_good, uint64_t* stop_offset);
+int wal_verify_host_walk(const uint8_t* h_wal, uint64_t size, uint64_t* n_good, uint64_t* stop_offset,
+                         std::vector<std::uint64_t>* good_pos = nullptr);
+
+// The largest sequence_ (u64 LE at record byte 9) of the records at pos[0, n); 0 for none (engine.cpp:17,46).
+std::uint64_t max_sequence_of(const std::uint8_t* w, const std::vector<std::uint64_t>& pos) {
+  std::uint64_t mx = 0;
+  for (const std::uint64_t p : pos) {
+    std::uint64_t seq;
+    std::memcpy(&seq, w + p + 9, 8);
+    mx = std::max(mx, seq);
+  }
+  return mx;
+}
 
 int sst_check(const std::uint64_t* h_sizes, std::uint64_t n) {
   for (std::uint64_t i = 0; i < n; ++i)
@@ -240,12 +252,67 @@ int tkv_wal_verify_device(const uint8_t* d_wal, uint64_t size, uint64_t* n_good,
   return wal_verify_host_walk(h.data(), size, n_good, stop_offset);
 }
 
+int tkv_wal_index_device(const uint8_t* d_wal, uint64_t size, uint64_t* d_off64, uint32_t* d_off32, uint64_t cap,
+                         uint64_t* n_good, uint64_t* stop_offset, uint64_t* max_sequence, void* stream) {
+  if ((size && !ptr_ok(d_wal)) || !ptr_ok(n_good) || !ptr_ok(stop_offset) || !ptr_ok(max_sequence))
+    return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  if (cap && !ptr_ok(d_off64) && !ptr_ok(d_off32))
+    return set_error(TKV_INVALID_ARGUMENT, "cap > 0 without an offsets array");
+  if (ptr_ok(d_off32) && size > 0xFFFFFFFFull + 1ull)
+    return set_error(TKV_INVALID_ARGUMENT, "image larger than 4 GiB (u32 offsets)");
+  *n_good = *stop_offset = *max_sequence = 0;
+  if (size == 0) return TKV_OK;
+  bool host_walk = false;
+  const int rc = wal_index_device_impl(d_wal, size, d_off64, d_off32, cap, n_good, stop_offset, max_sequence,
+                                       static_cast<hipStream_t>(stream), &host_walk);
+  if (!host_walk) return rc;
+  // the verify's exact fallback (tkv_wal_verify_device): its walk's positions go to the caller's arrays,
+  // the copies on the caller's stream
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::vector<std::uint8_t> h(size);
+  if (hipMemcpyAsync(h.data(), d_wal, size, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return set_error(TKV_IO_ERROR, "WAL image copy to host failed");
+  std::vector<std::uint64_t> pos;
+  const int rw = wal_verify_host_walk(h.data(), size, n_good, stop_offset, &pos);
+  if (rw != TKV_OK && rw != TKV_CORRUPTED) return rw;
+  *max_sequence = max_sequence_of(h.data(), pos);
+  const std::size_t n = static_cast<std::size_t>(std::min<std::uint64_t>(pos.size(), cap));
+  std::vector<std::uint32_t> p32;
+  if (n && ptr_ok(d_off32)) p32.assign(pos.begin(), pos.begin() + static_cast<std::ptrdiff_t>(n));
+  bool ok = true;
+  if (n && ptr_ok(d_off64)) ok = hipMemcpyAsync(d_off64, pos.data(), n * 8, hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok && n && ptr_ok(d_off32)) ok = hipMemcpyAsync(d_off32, p32.data(), n * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+  if (hipStreamSynchronize(st) != hipSuccess || !ok) return set_error(TKV_IO_ERROR, "WAL index copy to the device failed");
+  return rw;
+}
+
+int tkv_wal_index(const uint8_t* h_wal, uint64_t size, uint64_t* h_off64, uint64_t cap, uint64_t* n_good,
+                  uint64_t* stop_offset, uint64_t* max_sequence) {
+  if ((size && !ptr_ok(h_wal)) || !ptr_ok(n_good) || !ptr_ok(stop_offset) || !ptr_ok(max_sequence))
+    return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  if (cap && !ptr_ok(h_off64)) return set_error(TKV_INVALID_ARGUMENT, "cap > 0 without an offsets array");
+  *n_good = *stop_offset = *max_sequence = 0;
+  if (size == 0) return TKV_OK;
+  bool host_walk = false;
+  const int rc = wal_index_host_image_impl(h_wal, size, h_off64, cap, n_good, stop_offset, max_sequence, &host_walk);
+  if (!host_walk) return rc;
+  std::vector<std::uint64_t> pos;
+  const int rw = wal_verify_host_walk(h_wal, size, n_good, stop_offset, &pos);
+  if (rw != TKV_OK && rw != TKV_CORRUPTED) return rw;
+  *max_sequence = max_sequence_of(h_wal, pos);
+  const std::size_t n = static_cast<std::size_t>(std::min<std::uint64_t>(pos.size(), cap));
+  if (n) std::memcpy(h_off64, pos.data(), n * 8);
+  return rw;
+}
+
 }  // extern "C"
 
 namespace {
 // The host-walk verify (exact for every image): the record_len chain walked on host threads, the
 // CRCs checked on the GPU through the host batch API.
-int wal_verify_host_walk(const uint8_t* h_wal, uint64_t size, uint64_t* n_good, uint64_t* stop_offset) {
+// good_pos, when given, receives the starts of the good records (Chain::pos of the good prefix).
+int wal_verify_host_walk(const uint8_t* h_wal, uint64_t size, uint64_t* n_good, uint64_t* stop_offset,
+                         std::vector<std::uint64_t>* good_pos) {
   // The record_len chain (wal.cpp:63-87), walked in parallel (wal_chain): records are
   // [u32 record_len][u32 crc][payload of record_len bytes]. Large images go in phases: the CRC
   // batch of phase j runs (GPU, on a helper thread) while the host walks phase j+1.
@@ -292,6 +359,7 @@ int wal_verify_host_walk(const uint8_t* h_wal, uint64_t size, uint64_t* n_good, 
   while (good < nrec && all[good] == ch.crc[good] && ch.kv_ok[good]) ++good;
   *n_good = good;
   *stop_offset = good < nrec ? ch.pos[good] : ch.end;
+  if (good_pos) good_pos->assign(ch.pos.begin(), ch.pos.begin() + static_cast<std::ptrdiff_t>(good));
   if (good < nrec || ch.err) return set_error(TKV_CORRUPTED, "corrupted WAL record");
   return TKV_OK;
 }

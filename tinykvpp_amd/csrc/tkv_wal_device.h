@@ -23,4 +23,20 @@ int wal_verify_device_impl(const std::uint8_t* d_wal, std::uint64_t size, std::u
 int wal_verify_host_image_impl(const std::uint8_t* h_wal, std::uint64_t size, std::uint64_t* n_good,
                                std::uint64_t* stop_offset, bool* needs_host_walk);
 
+// wal_verify_device_impl, then the record index of the settled chain (tkv_wal_index_device): a scan of
+// the per-region good-record counts and one more read of the image that writes the start offsets of
+// the first min(*n_good, cap) good records, in chain order, to d_off64 / d_off32 (device; either may be
+// null) and reduces the largest sequence_ among the good records. Status, *n_good and *stop_offset are
+// the verify's. When *needs_host_walk is set nothing is indexed: the caller takes the positions from
+// the exact host walk.
+int wal_index_device_impl(const std::uint8_t* d_wal, std::uint64_t size, std::uint64_t* d_off64, std::uint32_t* d_off32,
+                          std::uint64_t cap, std::uint64_t* n_good, std::uint64_t* stop_offset, std::uint64_t* max_sequence,
+                          hipStream_t st, bool* needs_host_walk);
+
+// Host image: copied as wal_verify_host_image_impl does, indexed on the device copy, the offsets copied
+// back to h_off64 (host, cap entries).
+int wal_index_host_image_impl(const std::uint8_t* h_wal, std::uint64_t size, std::uint64_t* h_off64, std::uint64_t cap,
+                              std::uint64_t* n_good, std::uint64_t* stop_offset, std::uint64_t* max_sequence,
+                              bool* needs_host_walk);
+
 }  // namespace tkv

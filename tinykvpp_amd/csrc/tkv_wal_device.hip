@@ -37,6 +37,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
+#ifdef TKV_DEBUG
+#include <cassert>
+#endif
 #include <cstdint>
 #include <cstring>
 #include <mutex>
@@ -505,6 +509,8 @@ __device__ __forceinline__ void sweep_wave(const SweepArgs& a, std::uint8_t* win
       const P re = rs + kRegion;
       std::uint32_t ver = 0;
       if constexpr (FIXUP) ver = (a.fl[rr] >> 8) + 1u;
+      // (Steps 1 and 2 are restated for an exact entry in wal_idx_emit, which must walk a region to
+      // the same chain: a change to the starts, the link check or the repair here is made there too.)
       // ---- 1. starts ------------------------------------------------------------------------------
       const P ps = rs + static_cast<P>(kPiece) * lane, pe = ps + kPiece;
       const bool exact = e != kNo;
@@ -1099,6 +1105,240 @@ __global__ void wal_publish(SweepArgs a, std::uint64_t* h) {
   if (threadIdx.x == 0) publish_one(a, h);
 }
 
+// ---- record index (tkv_wal_index_device) -------------------------------------------
+// After a verify has settled the chain, the good records' start offsets in chain order and the largest
+// sequence_ among them (engine.cpp:17,46). Region i holds good[i] of them: what wal_finish counts into
+// n_good (cnt[i] before the stop region, and in the stop region unless the stop is a bad record: then
+// kResLidx, the records in front of it). A two-level exclusive scan of good[] over blocks of
+// kScanThreads regions (wal_idx_count: block sums; wal_idx_top: their scan, one block; wal_idx_base:
+// the per-region bases) gives every region its first index; wal_idx_emit then walks each region with a
+// non-zero count again, one wave per region, from its settled entry E[i], out of LDS. The image is read
+// a second time; the sweep is not touched.
+constexpr unsigned kScanThreads = 256;   // regions per block of the scan kernels (one per thread)
+constexpr unsigned kIdxWaves = 4;        // waves (regions) per workgroup of wal_idx_emit
+// window bytes behind the region: the search reads nine granules from a piece's start, a header's
+// fields end 26 bytes past a start (and the window starts up to 15 bytes in front of the region)
+constexpr std::uint32_t kIdxOver = 48;
+constexpr std::uint32_t kIdxWin = kRegion + kIdxOver;
+static_assert(kIdxOver % 16 == 0 && kIdxOver >= 15 + kWalMeta + 4 && kRegion - kPiece + 15 + 8 + 16 * 9 <= kIdxWin + 15,
+              "headers of records that start in the region, and the last piece's search, lie in the window");
+// index result words (device, u64)
+enum : int { kIdxMaxSeq = 0, kIdxTotal, kIdxIncons, kIdxWords };
+static_assert(9 + kIdxWords <= kHres, "the index words lie behind the verify's in the pinned result block");
+
+struct IndexArgs {
+  std::uint32_t* good;   // per region: good records that start in it
+  std::uint64_t* base;   // per region: good records in front of it (exclusive scan of good[])
+  std::uint64_t* rmax;   // per region with good records: the largest sequence_ among them (wal_idx_emit)
+  std::uint64_t* bsum;   // per scan block: its sum, then (wal_idx_top) the sum of the blocks before it
+  std::uint32_t nblk;
+  std::uint64_t* off64;  // outputs (either may be null), cap entries
+  std::uint32_t* off32;
+  std::uint64_t cap;
+  unsigned long long* ires;
+};
+
+__device__ __forceinline__ std::uint32_t region_good(const SweepArgs& a, std::uint64_t i) {
+  const std::uint64_t P = a.res[kResP], Q = a.res[kResQ];
+  const bool bad = P < Q;
+  const std::uint64_t stop = bad ? P : Q;
+  const std::uint64_t rb = stop == kNone ? a.nreg : stop / kRegion;
+  if (bad && i == rb) return static_cast<std::uint32_t>(a.res[kResLidx]);
+  return (a.fl[i] & kChain) && i <= rb ? a.cnt[i] : 0u;
+}
+
+// Exclusive prefix of v over the block's kScanThreads threads (DPP scan per wave, wave totals through
+// LDS) and the block's total.
+__device__ __forceinline__ std::uint32_t block_prefix(std::uint32_t v, std::uint32_t* total) {
+  __shared__ std::uint32_t wsum[kScanThreads / 64];
+  std::uint32_t wt;
+  const std::uint32_t pre = lane_prefix(v, &wt);
+  const std::uint32_t wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 0) wsum[wv] = wt;
+  __syncthreads();
+  std::uint32_t before = 0, all = 0;
+#pragma unroll
+  for (std::uint32_t k = 0; k < kScanThreads / 64; ++k) {
+    before += k < wv ? wsum[k] : 0u;
+    all += wsum[k];
+  }
+  *total = all;
+  return before + pre;
+}
+
+__global__ __launch_bounds__(kScanThreads) void wal_idx_count(SweepArgs a, IndexArgs x) {
+  const std::uint64_t i = blockIdx.x * static_cast<std::uint64_t>(kScanThreads) + threadIdx.x;
+  const std::uint32_t c = i < a.nreg ? region_good(a, i) : 0u;
+  if (i < a.nreg) x.good[i] = c;
+  std::uint32_t total;
+  (void)block_prefix(c, &total);
+  if (threadIdx.x == 0) x.bsum[blockIdx.x] = total;
+}
+
+// bsum[] <- its exclusive scan (one block: every thread a run of consecutive blocks); the total.
+__global__ __launch_bounds__(kScanThreads) void wal_idx_top(IndexArgs x) {
+  __shared__ std::uint64_t part[kScanThreads];
+  const std::uint32_t t = threadIdx.x;
+  const std::uint32_t per = (x.nblk + kScanThreads - 1u) / kScanThreads;
+  std::uint64_t s = 0;
+  for (std::uint32_t k = 0; k < per; ++k) {
+    const std::uint64_t b = static_cast<std::uint64_t>(t) * per + k;
+    if (b < x.nblk) s += x.bsum[b];
+  }
+  part[t] = s;
+  __syncthreads();
+  for (std::uint32_t d = 1; d < kScanThreads; d <<= 1) {
+    const std::uint64_t v = t >= d ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  std::uint64_t run = t ? part[t - 1] : 0;
+  for (std::uint32_t k = 0; k < per; ++k) {
+    const std::uint64_t b = static_cast<std::uint64_t>(t) * per + k;
+    if (b < x.nblk) {
+      const std::uint64_t v = x.bsum[b];
+      x.bsum[b] = run;
+      run += v;
+    }
+  }
+  if (t == kScanThreads - 1u) x.ires[kIdxTotal] = part[kScanThreads - 1u];
+}
+
+__global__ __launch_bounds__(kScanThreads) void wal_idx_base(SweepArgs a, IndexArgs x) {
+  const std::uint64_t i = blockIdx.x * static_cast<std::uint64_t>(kScanThreads) + threadIdx.x;
+  std::uint32_t total;
+  const std::uint32_t pre = block_prefix(i < a.nreg ? x.good[i] : 0u, &total);
+  if (i < a.nreg) x.base[i] = x.bsum[blockIdx.x] + pre;
+}
+
+// One wave per region with good records: the region and the kIdxOver bytes behind it into the wave's LDS
+// window (coalesced 16-byte buffer loads whose descriptor ends at the image's last granule, as
+// load_region), the region's chain from its settled entry as the sweep walks it (the entry's lane from
+// E, later lanes from their piece's first plausible header, the link repair: every read from LDS), then
+// the first good[r] starts in chain order to off64 / off32 [base[r] + k] below cap, and the largest
+// sequence_ (u64 LE at record byte 9) of those records, reduced across the wave into rmax[r] (wal_idx_max reduces the regions).
+// Good records are at least 26 bytes long, so a lane's good records are all among its stored starts.
+__global__ __launch_bounds__(64 * kIdxWaves) void wal_idx_emit(SweepArgs a, IndexArgs x) {
+  using P = std::uint64_t;
+  __shared__ __attribute__((aligned(16))) std::uint8_t wins[kIdxWaves][kIdxWin];
+  const std::uint32_t lane = threadIdx.x & 63u;
+  const std::uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const std::uint64_t r = blockIdx.x * static_cast<std::uint64_t>(kIdxWaves) + wv;
+  if (r >= a.nreg) return;
+  const std::uint32_t n = x.good[r];
+  const P rs = r * kRegion, re = rs + kRegion, size = a.size;
+  const P e = a.E[r];
+  if (n == 0) return;  // (no good record starts here: a region inside a record, past the stop, or without chain)
+  if (e < rs || e >= re || e >= size) {  // (never seen) records counted where the chain does not enter
+    if (lane == 0) atomicMax(&x.ires[kIdxIncons], 1ull);
+    return;
+  }
+  std::uint8_t* win = wins[wv];
+  const std::uint32_t o = a.o;
+  {
+    const std::uint64_t ad = a.al0 + rs;
+    const std::uint64_t base = static_cast<std::uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<std::uint32_t>(ad))) |
+                               static_cast<std::uint64_t>(static_cast<std::uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<std::uint32_t>(ad >> 32)))) << 32;
+    const std::uint64_t left = a.gend > base ? a.gend - base : 0u;
+    const std::uint32_t nrec = __builtin_amdgcn_readfirstlane(static_cast<std::uint32_t>(std::min<std::uint64_t>(left, kIdxWin)));
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(base), 0, nrec, 0x00020000);
+    uint4 g[kRows + 1];
+#pragma unroll
+    for (int k = 0; k <= kRows; ++k) {  // (row kRows: the bytes behind the region; past nrec: zeros, nothing fetched)
+      const auto v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 16u * lane + 1024u * k, 0, 0);
+      g[k] = uint4{v[0], v[1], v[2], v[3]};
+    }
+#pragma unroll
+    for (int k = 0; k < kRows; ++k) *reinterpret_cast<uint4*>(win + 1024u * k + 16u * lane) = g[k];
+    if (lane < kIdxOver / 16u) *reinterpret_cast<uint4*>(win + kRegion + 16u * lane) = g[kRows];
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  // the region's chain from e: sweep_wave steps 1 and 2 with an exact entry, restated here so that the
+  // sweep's code generation stays as it is; the two must stay the same walk (the host compares the
+  // emitted total with the verify's count, and a region that yields fewer records than cnt flags it)
+  const P ps = rs + static_cast<P>(kPiece) * lane, pe = ps + kPiece;
+  const std::uint32_t le = static_cast<std::uint32_t>((e - rs) / kPiece);
+  P s = kNone;
+  if (lane == le) s = e;
+  const P qend = size >= kWalMeta ? std::min<P>(pe, size - kWalMeta + 1u) : 0u;
+  if (lane > le && ps < qend) s = search_piece<P, 8>(win, rs, o, ps, qend, size);
+  Walk<P> wk;
+  walk_piece(win, rs, o, s, pe, size, true, wk);
+  std::uint64_t C = __ballot(s != kNone) & ~((1ull << le) - 1ull);
+  std::uint32_t cur = le;
+  for (;;) {
+    const std::uint64_t below = C & ((1ull << lane) - 1ull);
+    const std::uint32_t prev = below ? 63u - static_cast<std::uint32_t>(__builtin_clzll(below)) : lane;
+    const P xp = shfl_pos(wk.x, prev);
+    const bool bp = __shfl(static_cast<int>(wk.broke), static_cast<int>(prev), 64) != 0;
+    const bool mine = ((C >> lane) & 1ull) && lane > cur;
+    const std::uint64_t fails = __ballot(mine && (bp || xp != s));
+    std::uint32_t pv;  // the last lane known to be on the chain, whose exit must be followed
+    if (fails) {
+      const std::uint32_t l0 = static_cast<std::uint32_t>(__builtin_ctzll(fails));
+      pv = 63u - static_cast<std::uint32_t>(__builtin_clzll(C & ((1ull << l0) - 1ull)));
+    } else {
+      pv = 63u - static_cast<std::uint32_t>(__builtin_clzll(C));
+    }
+    const P xv = readlane_pos(wk.x, pv);
+    const bool bv = __builtin_amdgcn_readlane(static_cast<int>(wk.broke), static_cast<int>(pv)) != 0;
+    if (bv || xv >= re || xv >= size) {  // the chain breaks, leaves the region or ends at pv
+      C &= (2ull << pv) - 1ull;
+      break;
+    }
+    const std::uint32_t q = static_cast<std::uint32_t>((xv - rs) / kPiece);
+    C &= ~(((1ull << q) - 1ull) & ~((2ull << pv) - 1ull));  // lanes strictly between drop out
+    C |= 1ull << q;
+    const bool me = lane == q;
+    if (me) s = xv;
+    walk_piece(win, rs, o, s, pe, size, me, wk);
+    cur = q;
+  }
+  const bool on = (C >> lane) & 1ull;
+  std::uint32_t total;
+  const std::uint32_t pre = lane_prefix(on ? wk.n : 0u, &total);
+  const std::uint64_t b0 = x.base[r];
+  std::uint64_t mx = 0;
+#pragma unroll
+  for (std::uint32_t j = 0; j < kStore; ++j) {
+    if (on && j < wk.n && pre + j < n) {
+      const std::uint32_t b = wk.st[j] + o;
+      const std::uint64_t seq = rd32(win, b + 9u) | static_cast<std::uint64_t>(rd32(win, b + 13u)) << 32;
+      mx = std::max(mx, seq);
+      const std::uint64_t k = b0 + pre + j;
+      if (k < x.cap) {
+        if (x.off64) x.off64[k] = rs + wk.st[j];
+        if (x.off32) x.off32[k] = static_cast<std::uint32_t>(rs + wk.st[j]);
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) mx = std::max(mx, static_cast<std::uint64_t>(__shfl_xor(static_cast<long long>(mx), m, 64)));
+  if (lane == 0) {
+    x.rmax[r] = mx;
+    if (total < n) atomicMax(&x.ires[kIdxIncons], 1ull);  // (never seen) fewer records than the verify counted
+  }
+}
+
+// The largest sequence_ over the regions with good records: one atomic max per block of kScanThreads
+// regions. (One atomic per emit wave, all on one word, took 11 ns each: 1.7 ms for the 150 K regions of
+// a 1 GiB image, three times the verify)
+__global__ __launch_bounds__(kScanThreads) void wal_idx_max(SweepArgs a, IndexArgs x) {
+  __shared__ unsigned long long wmax[kScanThreads / 64];
+  const std::uint64_t i = blockIdx.x * static_cast<std::uint64_t>(kScanThreads) + threadIdx.x;
+  std::uint64_t mx = i < a.nreg && x.good[i] != 0u ? x.rmax[i] : 0u;
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) mx = std::max(mx, static_cast<std::uint64_t>(__shfl_xor(static_cast<long long>(mx), m, 64)));
+  if ((threadIdx.x & 63u) == 0) wmax[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (unsigned k = 1; k < kScanThreads / 64; ++k) mx = std::max<std::uint64_t>(mx, wmax[k]);
+    if (mx) atomicMax(&x.ires[kIdxMaxSeq], static_cast<unsigned long long>(mx));
+  }
+}
+
 // Per-device scratch, grown by doubling and kept between calls (guarded by mu).
 struct WalScratch {
   std::mutex mu;
@@ -1127,6 +1367,13 @@ struct WalScratch {
   hipStream_t st = nullptr;   // copies of host images
   hipStream_t stc = nullptr;  // device work on host images
   int ncu = 0;
+  // record index: per region good (u32) and base (u64); per scan block sums (u64); result words; the
+  // offsets of a host image's records
+  std::uint64_t cap_idx = 0, cap_bsum = 0, cap_off = 0;
+  void* idx = nullptr;
+  void* bsum = nullptr;
+  void* d_off = nullptr;
+  unsigned long long* ires = nullptr;
   ~WalScratch() {
     if (st) (void)hipStreamSynchronize(st);
     if (stc) (void)hipStreamSynchronize(stc);
@@ -1137,6 +1384,10 @@ struct WalScratch {
       if (slab_free[i]) (void)hipEventDestroy(slab_free[i]);
     }
     if (st) (void)hipStreamDestroy(st);
+    (void)hipFree(idx);
+    (void)hipFree(bsum);
+    (void)hipFree(d_off);
+    (void)hipFree(ires);
     (void)hipFree(regs);
     (void)hipFree(raw);
     (void)hipFree(dense);
@@ -1155,6 +1406,8 @@ struct WalScratch {
 // round, so the rounds are bounded by the boundaries; none of the adversarial images needs more than a
 // handful, and each round costs two host syncs.
 constexpr std::uint64_t kRoundBudget = 256;
+// the budget in force (tkv_debug_set_wal_round_budget: tests reach the host-walk hand-over with a small one)
+std::atomic<std::uint64_t> g_round_budget{kRoundBudget};
 
 std::mutex g_wal_mu;
 WalScratch* g_wal[64] = {};
@@ -1393,7 +1646,7 @@ int verify_locked(WalScratch& s, const std::uint8_t* w, std::uint64_t size, std:
       g_rounds[at + 4] = s.h_res[7];
       g_rounds[at + 5] = s.h_res[8];
       ++rounds;
-      if (rounds > kRoundBudget) {  // (never seen) the exact host walk decides instead
+      if (rounds > g_round_budget.load(std::memory_order_relaxed)) {  // (never seen) the exact host walk decides instead
         *needs_host_walk = true;
         g_last[0] = rounds;
         g_last[1] = 1;
@@ -1432,6 +1685,51 @@ int verify_locked(WalScratch& s, const std::uint8_t* w, std::uint64_t size, std:
   }
 }
 
+// verify_locked, then the record index of the settled chain (the wal_idx_* kernels) on `st`
+// (synchronous): the first min(*n_good, cap) starts to d_off64 / d_off32 (either may be null), the
+// largest sequence_ of the good records. Nothing is indexed when the verify hands over to the host
+// walk or fails. Caller holds s.mu.
+int index_locked(WalScratch& s, const std::uint8_t* w, std::uint64_t size, std::uint64_t* d_off64, std::uint32_t* d_off32,
+                 std::uint64_t cap, std::uint64_t* n_good, std::uint64_t* stop_offset, std::uint64_t* max_sequence,
+                 hipStream_t st, bool* needs_host_walk) {
+  const int rc = verify_locked(s, w, size, n_good, stop_offset, st, needs_host_walk);
+  if (*needs_host_walk || (rc != TKV_OK && rc != TKV_CORRUPTED)) return rc;
+  const std::uint32_t nreg = static_cast<std::uint32_t>((size + kRegion - 1) / kRegion);
+  const std::uint32_t nblk = blocks(nreg, kScanThreads);
+  if (int e = grow(&s.idx, &s.cap_idx, nreg, 8 + 8 + 4)) return e;
+  if (int e = grow(&s.bsum, &s.cap_bsum, nblk, 8)) return e;
+  if (!s.ires) WAL_HIP(hipMalloc(reinterpret_cast<void**>(&s.ires), kIdxWords * sizeof(unsigned long long)));
+  // the settled per-region arrays and result words (the long-payload fields are not used here)
+  const SweepArgs a = carve(s, w, size, nreg, 0, 0, nullptr);
+  IndexArgs x{};
+  x.base = static_cast<std::uint64_t*>(s.idx);
+  x.rmax = x.base + s.cap_idx;
+  x.good = reinterpret_cast<std::uint32_t*>(x.rmax + s.cap_idx);
+  x.bsum = static_cast<std::uint64_t*>(s.bsum);
+  x.nblk = nblk;
+  x.off64 = d_off64;
+  x.off32 = d_off32;
+  x.cap = cap;
+  x.ires = s.ires;
+  WAL_HIP(hipMemsetAsync(s.ires, 0, kIdxWords * sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(wal_idx_count, dim3(nblk), dim3(kScanThreads), 0, st, a, x);
+  hipLaunchKernelGGL(wal_idx_top, dim3(1), dim3(kScanThreads), 0, st, x);
+  hipLaunchKernelGGL(wal_idx_base, dim3(nblk), dim3(kScanThreads), 0, st, a, x);
+  hipLaunchKernelGGL(wal_idx_emit, dim3(blocks(nreg, kIdxWaves)), dim3(64 * kIdxWaves), 0, st, a, x);
+  hipLaunchKernelGGL(wal_idx_max, dim3(nblk), dim3(kScanThreads), 0, st, a, x);
+  WAL_HIP(hipGetLastError());
+  std::uint64_t* h = s.h_res + kHres - kIdxWords;  // (the verify's result words are read; these lie behind them)
+  WAL_HIP(hipMemcpyAsync(h, s.ires, kIdxWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  WAL_HIP(hipStreamSynchronize(st));
+  const bool consistent = h[kIdxTotal] == *n_good && h[kIdxIncons] == 0;
+#ifdef TKV_DEBUG
+  assert(consistent && "WAL index: the region counts do not add up to the verify's n_good");
+#endif
+  if (!consistent) return set_error(TKV_IO_ERROR, "WAL index: the region counts do not add up to the verify's record count");
+  *max_sequence = h[kIdxMaxSeq];
+  return rc;
+}
+
 // memcpy of a large range into pinned staging on several host threads.
 void stage_copy(std::uint8_t* dst, const std::uint8_t* src, std::uint64_t n) {
   const unsigned nt = n >= (std::uint64_t(16) << 20) ? 8u : 1u;
@@ -1452,8 +1750,8 @@ constexpr std::uint64_t kStageSlab = std::uint64_t(64) << 20;
 // Device copies of host images up to this size stay allocated between verifies.
 constexpr std::uint64_t kKeepImg = std::uint64_t(256) << 20;
 
-int host_image_locked(WalScratch& s, const std::uint8_t* h_wal, std::uint64_t size, std::uint64_t* n_good,
-                      std::uint64_t* stop_offset, bool* needs_host_walk) {
+// The host image into the device buffer s.d_img (synchronous). *needs_host_walk: the device cannot hold it.
+int host_image_copy_locked(WalScratch& s, const std::uint8_t* h_wal, std::uint64_t size, bool* needs_host_walk) {
   if (size > s.cap_img) {
     (void)hipStreamSynchronize(s.st);
     (void)hipFree(s.d_img);
@@ -1490,7 +1788,35 @@ int host_image_locked(WalScratch& s, const std::uint8_t* h_wal, std::uint64_t si
     }
   }
   WAL_HIP(hipStreamSynchronize(s.st));
+  return TKV_OK;
+}
+
+int host_image_locked(WalScratch& s, const std::uint8_t* h_wal, std::uint64_t size, std::uint64_t* n_good,
+                      std::uint64_t* stop_offset, bool* needs_host_walk) {
+  if (int rc = host_image_copy_locked(s, h_wal, size, needs_host_walk)) return rc;
+  if (*needs_host_walk) return TKV_OK;
   return verify_locked(s, s.d_img, size, n_good, stop_offset, s.stc, needs_host_walk);
+}
+
+// Host image: copied as for the verify, indexed on the device copy into a device array of
+// min(cap, size / 26) offsets (a good record is at least 26 bytes long), which come back to h_off64.
+int host_index_locked(WalScratch& s, const std::uint8_t* h_wal, std::uint64_t size, std::uint64_t* h_off64, std::uint64_t cap,
+                      std::uint64_t* n_good, std::uint64_t* stop_offset, std::uint64_t* max_sequence, bool* needs_host_walk) {
+  if (int rc = host_image_copy_locked(s, h_wal, size, needs_host_walk)) return rc;
+  if (*needs_host_walk) return TKV_OK;
+  const std::uint64_t dcap = std::min<std::uint64_t>(cap, size / kWalMeta);
+  if (grow(&s.d_off, &s.cap_off, dcap, 8) != TKV_OK) {
+    (void)hipGetLastError();  // the offsets do not fit the device: exact host walk, as for the image itself
+    *needs_host_walk = true;
+    g_last[1] = 1;
+    return TKV_OK;
+  }
+  const int rc = index_locked(s, s.d_img, size, dcap ? static_cast<std::uint64_t*>(s.d_off) : nullptr, nullptr, dcap, n_good,
+                              stop_offset, max_sequence, s.stc, needs_host_walk);
+  if (*needs_host_walk || (rc != TKV_OK && rc != TKV_CORRUPTED)) return rc;
+  const std::uint64_t n = std::min<std::uint64_t>(*n_good, dcap);
+  if (n) WAL_HIP(hipMemcpy(h_off64, s.d_off, n * 8, hipMemcpyDeviceToHost));
+  return rc;
 }
 
 }  // namespace
@@ -1537,10 +1863,63 @@ int wal_verify_host_image_impl(const std::uint8_t* h_wal, std::uint64_t size, st
   return rc;
 }
 
+int wal_index_device_impl(const std::uint8_t* d_wal, std::uint64_t size, std::uint64_t* d_off64, std::uint32_t* d_off32,
+                          std::uint64_t cap, std::uint64_t* n_good, std::uint64_t* stop_offset, std::uint64_t* max_sequence,
+                          hipStream_t st, bool* needs_host_walk) {
+  *needs_host_walk = false;
+  *n_good = 0;
+  *stop_offset = 0;
+  *max_sequence = 0;
+  g_last[0] = g_last[1] = g_last[2] = g_last[3] = 0;
+  g_rounds.clear();
+  if (size == 0) return TKV_OK;
+  WalScratch* sp = nullptr;
+  if (int rc = scratch(&sp)) return rc;
+  WalScratch& s = *sp;
+  std::lock_guard<std::mutex> lk(s.mu);
+  return index_locked(s, d_wal, size, d_off64, d_off32, cap, n_good, stop_offset, max_sequence, st, needs_host_walk);
+}
+
+int wal_index_host_image_impl(const std::uint8_t* h_wal, std::uint64_t size, std::uint64_t* h_off64, std::uint64_t cap,
+                              std::uint64_t* n_good, std::uint64_t* stop_offset, std::uint64_t* max_sequence,
+                              bool* needs_host_walk) {
+  *needs_host_walk = false;
+  *n_good = 0;
+  *stop_offset = 0;
+  *max_sequence = 0;
+  g_last[0] = g_last[1] = g_last[2] = g_last[3] = 0;
+  g_rounds.clear();
+  if (size == 0) return TKV_OK;
+  WalScratch* sp = nullptr;
+  if (int rc = scratch(&sp)) return rc;
+  WalScratch& s = *sp;
+  std::lock_guard<std::mutex> lk(s.mu);
+  g_last[2] = 1;
+  const int rc = host_index_locked(s, h_wal, size, h_off64, cap, n_good, stop_offset, max_sequence, needs_host_walk);
+  // as wal_verify_host_image_impl: nothing outlives the call, large buffers are released
+  (void)hipStreamSynchronize(s.st);
+  (void)hipStreamSynchronize(s.stc);
+  if (s.cap_img > kKeepImg) {
+    (void)hipFree(s.d_img);
+    s.d_img = nullptr;
+    s.cap_img = 0;
+  }
+  if (s.cap_off * 8 > kKeepImg) {
+    (void)hipFree(s.d_off);
+    s.d_off = nullptr;
+    s.cap_off = 0;
+  }
+  return rc;
+}
+
 }  // namespace tkv
 
 extern "C" void tkv_debug_wal_last(uint64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tkv::g_last[i];
+}
+
+extern "C" uint64_t tkv_debug_set_wal_round_budget(uint64_t rounds) {
+  return tkv::g_round_budget.exchange(rounds ? rounds : tkv::kRoundBudget);
 }
 
 extern "C" size_t tkv_debug_wal_rounds(uint64_t* out, size_t n) {

@@ -87,6 +87,61 @@ def verify_device(image, size=None, stream=None):
     return ("ok" if rc == OK else "corrupted"), good.value, stop.value
 
 
+def index(wal_bytes):
+    """Verify a slurped WAL image and list its good records (tkv_wal_index): what engine::create's
+    recovery loop needs (engine.cpp:31-53). Returns (status, offsets, stop_offset, max_sequence):
+    status and stop_offset as verify(), offsets a uint64 numpy array of the n_good good records' start
+    offsets in chain order, max_sequence the largest sequence_ among them (0 for none)."""
+    if isinstance(wal_bytes, np.ndarray):
+        buf = np.ascontiguousarray(wal_bytes).reshape(-1).view(np.uint8)
+    else:
+        buf = np.frombuffer(wal_bytes, np.uint8)
+    cap = buf.size // kMetadataSize  # a good record is at least 26 bytes long
+    offs = np.empty(cap, np.uint64)
+    good, stop, seq = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = load_library().tkv_wal_index(ctypes.c_void_p(buf.ctypes.data) if buf.size else None, buf.size,
+                                      ctypes.c_void_p(offs.ctypes.data) if cap else None, cap,
+                                      ctypes.byref(good), ctypes.byref(stop), ctypes.byref(seq))
+    if rc not in (OK, CORRUPTED):
+        check(rc)
+    return ("ok" if rc == OK else "corrupted"), offs[:good.value], stop.value, seq.value
+
+
+def index_device(image, size=None, out=None, offsets32=False, stream=None):
+    """Verify a WAL image held in a uint8 CUDA tensor (first ``size`` bytes; default all) and list its
+    good records on the device (tkv_wal_index_device). Returns (status, offsets, stop_offset,
+    max_sequence): offsets is ``out[:n_good]``, the good records' start offsets in chain order, an int64
+    CUDA tensor, or an int32 one (u32 offsets, images up to 4 GiB: what check_records_device takes) with
+    ``offsets32``. ``out`` (of that dtype) is allocated with size // 26 entries when not given; one with
+    fewer entries than there are good records is an error (the C call reports the full count)."""
+    import torch
+    if image.dtype != torch.uint8 or not image.is_cuda or not image.is_contiguous():
+        raise ValueError("image must be a contiguous uint8 CUDA tensor")
+    n = image.numel() if size is None else int(size)
+    if n > image.numel():
+        raise ValueError("size exceeds the tensor")
+    from .crc32 import _check_data, _check_vec, _launch_stream
+    _check_data(image)
+    dtype = torch.int32 if offsets32 else torch.int64
+    if out is None:
+        out = torch.empty(n // kMetadataSize, dtype=dtype, device=image.device)
+        if stream is not None and stream != torch.cuda.current_stream(image.device):
+            out.record_stream(stream)
+    _check_vec("out", out, dtype, 0, image.device)
+    cap = out.numel()
+    st = _launch_stream(stream, image.device)
+    ptr = ctypes.c_void_p(out.data_ptr()) if cap else None
+    good, stop, seq = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = load_library().tkv_wal_index_device(ctypes.c_void_p(image.data_ptr()), n, None if offsets32 else ptr,
+                                             ptr if offsets32 else None, cap, ctypes.byref(good),
+                                             ctypes.byref(stop), ctypes.byref(seq), st)
+    if rc not in (OK, CORRUPTED):
+        check(rc)
+    if good.value > cap:
+        raise ValueError(f"out holds {cap} offsets, the image has {good.value} good records")
+    return ("ok" if rc == OK else "corrupted"), out[:good.value], stop.value, seq.value
+
+
 def check_records_device(image, rec_offsets, max_payload=64, crc_out=None, first_bad=None, stream=None):
     """wal_entry::decode's per-record checks (wal.cpp:63-127) for records whose starts are known:
     ``image`` a uint8 CUDA tensor, ``rec_offsets`` an int32/uint32 CUDA tensor of record start offsets
