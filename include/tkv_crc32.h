@@ -342,6 +342,12 @@ int tkv_debug_set_stream_groups(int enable);
  * smaller batches do (kept so the general path's large-batch shapes stay under test). Returns the
  * previous setting. Default 1. */
 int tkv_debug_set_one_pass(int enable);
+/* Packed uniform CRC-32 batches (blocks a multiple of 4 KiB, back to back, 16-byte aligned) fold 24 of
+ * every lane's 64 bytes away with shifts and XORs modulo a sparse multiple of the polynomial before
+ * the table steps unless this is 0: then they take the table-only kernel, as CRC-32C
+ * always does (kept so one process can run both on the same buffers). Returns the previous setting.
+ * Default 1. */
+int tkv_debug_set_packed_fold(int enable);
 
 
 #ifdef __cplusplus

@@ -77,6 +77,7 @@ SIGNATURES = {
     "tkv_debug_set_host_mapped": (_int, [_int]),
     "tkv_debug_set_stream_groups": (_int, [_int]),
     "tkv_debug_set_one_pass": (_int, [_int]),
+    "tkv_debug_set_packed_fold": (_int, [_int]),
     "tkv_debug_wal_chain": (_sz, [_u8p, _u64, _vp, _sz, ctypes.POINTER(_u64), ctypes.POINTER(_int)]),
     "tkv_debug_wal_last": (None, [_vp]),
     "tkv_debug_wal_rounds": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
@@ -93,7 +94,8 @@ SIGNATURES = {
 }
 
 # symbols an older build may lack (tools/ab_lib.py loads earlier builds for A/B runs)
-OPTIONAL = {"tkv_build_id", "tkv_wal_index_device", "tkv_wal_index", "tkv_debug_set_wal_round_budget"}
+OPTIONAL = {"tkv_build_id", "tkv_wal_index_device", "tkv_wal_index", "tkv_debug_set_wal_round_budget",
+            "tkv_debug_set_packed_fold"}
 
 _lib = None
 

@@ -10,6 +10,7 @@
 
 #include <type_traits>
 
+#include "tkv_crc32_fold.h"
 #include "tkv_crc32_internal.h"
 
 namespace tkv {
@@ -119,6 +120,24 @@ __device__ __forceinline__ std::uint32_t lane_shift(const std::uint32_t* lds, st
 #pragma unroll
   for (int j = 0; j < 8; ++j) l[j] = lds_at(lds, k.lsbase + 4096u * j + (((p >> (4 * j)) & 15u) << 8));
   return xor3(xor3(l[0], l[1], l[2]), xor3(l[3], l[4], l[5]), l[6] ^ l[7]);
+}
+
+// A lane's segment as loaded (four uint4 of a row buffer) to the 16 dwords the fold works on, and the
+// fold itself (tkv_crc32_fold.h: v_alignbit_b32, shifts and three-input XORs, no lookups): afterwards
+// crc_0(d[6..15]) = crc_0(segment), so kKeptDwords slice4 steps from Reg{0, 0} give the lane partial.
+// CRC-32 (0xEDB88320) tables only.
+__device__ __forceinline__ void segment_dwords(const uint4 (&q)[4], std::uint32_t (&d)[fold::kSegDwords]) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    d[4 * t] = q[t].x;
+    d[4 * t + 1] = q[t].y;
+    d[4 * t + 2] = q[t].z;
+    d[4 * t + 3] = q[t].w;
+  }
+}
+__device__ __forceinline__ void fold_segment(const uint4 (&q)[4], std::uint32_t (&d)[fold::kSegDwords]) {
+  segment_dwords(q, d);
+  fold::fold_segment(d);
 }
 
 
@@ -980,7 +999,9 @@ __device__ __forceinline__ void crc_stream_body(const RowsArgs& a, std::uint32_t
 // ranges, slots 12-15 the smallest, matching the issue arbitration that favours a SIMD's older waves.
 // PRIO (0: off): set_prio_from_left<PRIO> once per DEPTH rows (the product uses 3, and SKEW 154 for
 // blocks of more than one row; tkv_crc32_kernels.hip).
-template <int DEPTH, int ILP, bool R1, int SKEW = 0, int PRIO = 0>
+// FOLD: each lane first shortens its 64 bytes to 40 with the sparse-multiple fold (fold_segment above;
+// CRC-32 tables only), so a row costs 48 slicing lookups instead of 72.
+template <int DEPTH, int ILP, bool R1, int SKEW = 0, int PRIO = 0, bool FOLD = false>
 __device__ __forceinline__ void crc_packed_body(const RowsArgs& a, std::uint32_t* lds) {
   static_assert(DEPTH > ILP && DEPTH % ILP == 0, "DEPTH must be a multiple of ILP and exceed it");
   const std::uint32_t lane = threadIdx.x & 63u;
@@ -1080,16 +1101,31 @@ __device__ __forceinline__ void crc_packed_body(const RowsArgs& a, std::uint32_t
         Reg p[ILP];
 #pragma unroll
         for (int i = 0; i < ILP; ++i) p[i] = Reg{0, 0};
+        if constexpr (FOLD) {
+          std::uint32_t d[ILP][fold::kSegDwords];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
+          for (int i = 0; i < ILP; ++i) segment_dwords(buf[q + i], d[i]);
 #pragma unroll
-          for (int i = 0; i < ILP; ++i) slice4(lds, p[i], buf[q + i][t].x, kc);
+          for (int i = 0; i < ILP; ++i) fold::fold_stage0(d[i]);
 #pragma unroll
-          for (int i = 0; i < ILP; ++i) slice4(lds, p[i], buf[q + i][t].y, kc);
+          for (int i = 0; i < ILP; ++i) fold::fold_stage1(d[i]);
 #pragma unroll
-          for (int i = 0; i < ILP; ++i) slice4(lds, p[i], buf[q + i][t].z, kc);
+          for (int t = fold::kFoldedDwords; t < fold::kSegDwords; ++t) {
 #pragma unroll
-          for (int i = 0; i < ILP; ++i) slice4(lds, p[i], buf[q + i][t].w, kc);
+            for (int i = 0; i < ILP; ++i) slice4(lds, p[i], d[i][t], kc);
+          }
+        } else {
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+#pragma unroll
+            for (int i = 0; i < ILP; ++i) slice4(lds, p[i], buf[q + i][t].x, kc);
+#pragma unroll
+            for (int i = 0; i < ILP; ++i) slice4(lds, p[i], buf[q + i][t].y, kc);
+#pragma unroll
+            for (int i = 0; i < ILP; ++i) slice4(lds, p[i], buf[q + i][t].z, kc);
+#pragma unroll
+            for (int i = 0; i < ILP; ++i) slice4(lds, p[i], buf[q + i][t].w, kc);
+          }
         }
 #pragma unroll
         for (int i = 0; i < ILP; ++i) v[i] = lane_shift(lds, p[i].value(), kc);
@@ -1100,12 +1136,19 @@ __device__ __forceinline__ void crc_packed_body(const RowsArgs& a, std::uint32_t
         for (int i = 0; i < ILP; ++i) {  // tail: fewer than ILP rows left
           if (jq + i < nrows) {
             Reg p{0, 0};
+            if constexpr (FOLD) {
+              std::uint32_t d[fold::kSegDwords];
+              fold_segment(buf[q + i], d);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-              slice4(lds, p, buf[q + i][t].x, kc);
-              slice4(lds, p, buf[q + i][t].y, kc);
-              slice4(lds, p, buf[q + i][t].z, kc);
-              slice4(lds, p, buf[q + i][t].w, kc);
+              for (int t = fold::kFoldedDwords; t < fold::kSegDwords; ++t) slice4(lds, p, d[t], kc);
+            } else {
+#pragma unroll
+              for (int t = 0; t < 4; ++t) {
+                slice4(lds, p, buf[q + i][t].x, kc);
+                slice4(lds, p, buf[q + i][t].y, kc);
+                slice4(lds, p, buf[q + i][t].z, kc);
+                slice4(lds, p, buf[q + i][t].w, kc);
+              }
             }
             finish(lane_shift(lds, p.value(), kc));
           }

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "tkv_crc32.h"
+#include "tkv_crc32_fold.h"
 #include "tkv_crc32_internal.h"
 #include "tkv_engine.h"
 
@@ -27,7 +28,7 @@ namespace tkv {
 // ---- launchers (tkv_crc32_kernels.hip) ---------------------------------------------------------
 hipError_t launch_rows(const RowsArgs& a, bool aligned, bool uniform, unsigned grid, hipStream_t st);
 hipError_t launch_fixup(const RowsArgs& a, hipStream_t st);
-hipError_t launch_packed(const RowsArgs& a, unsigned grid, hipStream_t st);
+hipError_t launch_packed(const RowsArgs& a, bool fold, unsigned grid, hipStream_t st);
 std::uint32_t packed_small_group(std::uint32_t len);
 hipError_t launch_packed_small(const RowsArgs& a, unsigned grid, hipStream_t st);
 hipError_t launch_lanes(const RowsArgs& a, unsigned ncu, hipStream_t st);
@@ -437,6 +438,10 @@ RowsArgs base_args(DevCtx* c, StreamScratch* s, int algo) {
   return a;
 }
 
+// Whether packed CRC-32 batches take the kernel with the segment fold (tkv_debug_set_packed_fold;
+// default 1).
+std::atomic<int> g_packed_fold{1};
+
 // Uniform batches with len <= lane_max() take crc_lanes: kLaneMax.
 long long lane_max() { return static_cast<long long>(kLaneMax); }
 
@@ -466,7 +471,9 @@ int run_uniform(DevCtx* c, int algo, const std::uint8_t* d_base, std::uint64_t s
   if (aligned && n >= packed_waves && len != 0 && len % kRow == 0 && stride == len) {
     a.nwaves = static_cast<std::uint32_t>(packed_waves);
     a.snap_blocks = 1;
-    TKV_HIP(launch_packed(a, static_cast<unsigned>(c->ncu), st));  // whole blocks per wave, no seams
+    // whole blocks per wave, no seams; the segment fold needs CRC-32's polynomial
+    const bool fold = g_packed_fold.load(std::memory_order_relaxed) != 0 && algo_poly(algo) == fold::kFoldPoly;
+    TKV_HIP(launch_packed(a, fold, static_cast<unsigned>(c->ncu), st));
     return TKV_OK;
   }
   // (aligned back-to-back 64-byte blocks: crc_packed_small's exact G = 1 kernel is faster, 4477 vs
@@ -1430,5 +1437,7 @@ int tkv_debug_set_host_mapped(int enable) { return tkv::g_host_mapped.exchange(e
 int tkv_debug_set_stream_groups(int enable) { return tkv::g_stream_groups.exchange(enable ? 1 : 0); }
 
 int tkv_debug_set_one_pass(int enable) { return tkv::g_one_pass.exchange(enable ? 1 : 0); }
+
+int tkv_debug_set_packed_fold(int enable) { return tkv::g_packed_fold.exchange(enable ? 1 : 0); }
 
 }  // extern "C"

@@ -166,11 +166,13 @@ constexpr int kPackedIlp = 2;
 constexpr int kPackedSkew = 154;
 constexpr int kPackedPrio = 3;  // set_prio_from_left thresholds 1/4, 1/8, 1/16
 
-template <bool R1>
+// FOLD (CRC-32 tables only; launch_packed): the lanes fold 24 of their 64 bytes away with shifts and
+// XORs before the table steps (tkv_crc32_fold.h).
+template <bool R1, bool FOLD>
 __global__ __launch_bounds__(kThreads) void crc_packed(RowsArgs a) {
   static_assert(kThreads == 1024, "the skewed partition assumes 16 waves per workgroup");
   __shared__ std::uint32_t lds[kLdsWords];
-  dev::crc_packed_body<kPackedDepth, kPackedIlp, R1, R1 ? 0 : kPackedSkew, kPackedPrio>(a, lds);
+  dev::crc_packed_body<kPackedDepth, kPackedIlp, R1, R1 ? 0 : kPackedSkew, kPackedPrio, FOLD>(a, lds);
 }
 
 // Packed small blocks (len = 64 G <= 2 KiB for a power of two G, stride == len, 16-byte aligned,
@@ -1400,9 +1402,15 @@ hipError_t launch_rows(const RowsArgs& a, bool aligned, bool uniform, unsigned g
   return hipGetLastError();
 }
 
-hipError_t launch_packed(const RowsArgs& a, unsigned grid, hipStream_t st) {
-  if (a.len == kRow) hipLaunchKernelGGL(crc_packed<true>, dim3(grid), dim3(kThreads), 0, st, a);
-  else hipLaunchKernelGGL(crc_packed<false>, dim3(grid), dim3(kThreads), 0, st, a);
+// fold: the caller's tables are CRC-32's (0xEDB88320) and the segment fold is switched on
+hipError_t launch_packed(const RowsArgs& a, bool fold, unsigned grid, hipStream_t st) {
+  if (a.len == kRow) {
+    if (fold) hipLaunchKernelGGL((crc_packed<true, true>), dim3(grid), dim3(kThreads), 0, st, a);
+    else hipLaunchKernelGGL((crc_packed<true, false>), dim3(grid), dim3(kThreads), 0, st, a);
+  } else {
+    if (fold) hipLaunchKernelGGL((crc_packed<false, true>), dim3(grid), dim3(kThreads), 0, st, a);
+    else hipLaunchKernelGGL((crc_packed<false, false>), dim3(grid), dim3(kThreads), 0, st, a);
+  }
   return hipGetLastError();
 }
 

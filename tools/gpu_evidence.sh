@@ -15,7 +15,7 @@ for C in cfg2 cfg4; do
   timeout -k 10 -s KILL 300 rocprofv3 --kernel-trace --stats -d $O/trace_$C -o run --output-format csv -- python3 $B --config $C > $O/trace_$C.log 2>&1
   rc=$?; echo "trace $C rc=$rc"; if [ $rc -ne 0 ]; then tail -5 $O/trace_$C.log; exit $rc; fi
 done
-python3 $R/tools/trace_timed.py $(find $O/trace_cfg2 -name "*kernel_trace.csv" | head -1) 'crc_packed<true>' 200 > $O/cfg2_timed.json && cat $O/cfg2_timed.json
+python3 $R/tools/trace_timed.py $(find $O/trace_cfg2 -name "*kernel_trace.csv" | head -1) 'crc_packed<true,' 200 > $O/cfg2_timed.json && cat $O/cfg2_timed.json
 python3 $R/tools/trace_timed.py $(find $O/trace_cfg4 -name "*kernel_trace.csv" | head -1) 'crc_stream' 200 > $O/cfg4_timed.json && cat $O/cfg4_timed.json
 for C in cfg2 cfg3 cfg4 cfg5; do
   timeout -k 10 -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_$C -o pmc --output-format csv -- python3 $B --config $C --steps 5 --warmup 2 --min-warmup-ms 0 > $O/pmc_$C.log 2>&1

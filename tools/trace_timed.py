@@ -4,7 +4,7 @@ kernel whose name contains PATTERN (a bench's timed steps follow its warm-up and
 kernel runs after them), their average duration and their span per step, beside the average over
 every dispatch (warm-up included, as the --stats summary reports it).
 
-    python tools/trace_timed.py run_kernel_trace.csv 'crc_packed<true>' 200
+    python tools/trace_timed.py run_kernel_trace.csv 'crc_packed<true,' 200
 """
 import csv
 import json
