@@ -180,6 +180,47 @@ int tkv_wal_index(const uint8_t *h_wal, uint64_t size, uint64_t *h_off64, uint64
  * h_sizes[i] (>= 8), write crc32 of bytes [8, size) LE at offset 4 (wal.cpp:54-58). */
 int tkv_wal_stamp(uint8_t *h_buf, const uint64_t *h_offsets, const uint32_t *h_sizes, uint64_t n);
 
+/* ---- WAL group-commit encode (batch encode) ------------------------------- */
+
+/* wal_entry::encode (wal.cpp:19-61) for a batch of n records held as arenas: key i is
+ * [keys + key_off[i], + key_len[i]), value i is [vals + val_off[i], + val_len[i]). Sources may have any
+ * alignment, may have gaps and may overlap each other (many records may share one key); they do not
+ * overlap the destination. Record i is written exactly as the reference writes it, little-endian:
+ *     u32 record_len = 18 + key_len + val_len | u32 crc32 | u8 op | u64 seq | u8 tombstone |
+ *     u32 key_len | u32 val_len | key | value
+ * with crc32 the finalized CRC-32 of bytes [8, 26 + key_len + val_len) (wal.cpp:54-58). Records lie
+ * back to back in batch order, record 0 at img[0].
+ * Defaults: val_len == NULL: every value is empty (vals / val_off ignored); op == NULL: every op byte
+ * 0 (put); tomb == NULL: every tombstone byte 0; seq == NULL: seq[i] = first_seq + i (otherwise
+ * first_seq is ignored). The tombstone byte is written as 0 or 1 (nonzero input becomes 1), the op
+ * byte as given.
+ * img may have any byte alignment (a caller appends at the tail of an image it holds); no byte outside
+ * [img, img + total) is written or read-modify-written, total = sum of (26 + key_len + val_len).
+ * *img_size = total whenever the arguments are valid. total > cap: TKV_BUFFER_OVERFLOW, and nothing is
+ * written to img, rec_off or crc (cap = 0 with img = NULL is the sizing call). 18 + key_len + val_len
+ * beyond u32 for some record: TKV_INVALID_ARGUMENT, nothing written, no source byte read (the
+ * reference would wrap silently). rec_off (nullable): start offset of record i, n entries. crc
+ * (nullable): the stamped CRC of record i. n == 0: TKV_OK, *img_size = 0, nothing touched.
+ * n > 2^32 - 1, or NULL where a pointer is required (keys, key_off, key_len, img_size; vals and
+ * val_off with val_len): TKV_INVALID_ARGUMENT.
+ * The device call is synchronous on `stream` (the host needs total before the emit); with no usable
+ * GPU it returns TKV_IO_ERROR. No CRC is computed on the CPU in either call. */
+int tkv_wal_encode_device(const uint8_t *d_keys, const uint64_t *d_key_off, const uint32_t *d_key_len,
+                          const uint8_t *d_vals, const uint64_t *d_val_off, const uint32_t *d_val_len,
+                          const uint8_t *d_op, const uint8_t *d_tomb, const uint64_t *d_seq, uint64_t first_seq,
+                          uint64_t n, uint8_t *d_img, uint64_t cap, uint64_t *d_rec_off, uint32_t *d_crc,
+                          uint64_t *img_size, void *stream);
+
+/* The same with every argument in HOST memory. Sizes and offsets are computed and the records laid
+ * out (CRC fields zero) on host threads; the CRCs come from the path tkv_wal_stamp uses (pinned
+ * memory is read in place), then the fields are stored. Sizing, overflow and argument errors are
+ * decided before any GPU call. */
+int tkv_wal_encode(const uint8_t *h_keys, const uint64_t *h_key_off, const uint32_t *h_key_len,
+                   const uint8_t *h_vals, const uint64_t *h_val_off, const uint32_t *h_val_len,
+                   const uint8_t *h_op, const uint8_t *h_tomb, const uint64_t *h_seq, uint64_t first_seq,
+                   uint64_t n, uint8_t *h_img, uint64_t cap, uint64_t *h_rec_off, uint32_t *h_crc,
+                   uint64_t *img_size);
+
 /* ---- SSTable data-block stamping (the format is defined here) ----------- */
 
 /* The reference writes sstable_data_block_header::crc32_ = 0 (sstable_writer.cpp:138-144) and never
@@ -348,6 +389,26 @@ int tkv_debug_set_one_pass(int enable);
  * always does (kept so one process can run both on the same buffers). Returns the previous setting.
  * Default 1. */
 int tkv_debug_set_packed_fold(int enable);
+/* The host layout step of tkv_wal_encode alone (no GPU): the records with their CRC fields zero, what
+ * wal.cpp:27-52 leaves before line 54. Arguments as tkv_wal_encode; returns the number of records laid
+ * out (0 on an argument error or when total > cap) and sets *img_size as tkv_wal_encode does. */
+size_t tkv_debug_wal_encode_layout(const uint8_t *h_keys, const uint64_t *h_key_off, const uint32_t *h_key_len,
+                                   const uint8_t *h_vals, const uint64_t *h_val_off, const uint32_t *h_val_len,
+                                   const uint8_t *h_op, const uint8_t *h_tomb, const uint64_t *h_seq,
+                                   uint64_t first_seq, uint64_t n, uint8_t *h_img, uint64_t cap,
+                                   uint64_t *img_size);
+/* Geometry of tkv_wal_encode_device: out[0] = image bytes per emit tile, out[1] = records per
+ * workgroup of the size scan, out[2] = the largest record_len that is always stamped inside the emit
+ * pass, out[3] = number of scan levels (for 2^32 - 1 records). */
+void tkv_debug_wal_encode_geometry(uint64_t out[4]);
+/* What the calling thread's last tkv_wal_encode_device did: out[0] = records stamped inside the emit
+ * pass, out[1] = records stamped by reading the written image back, out[2] = emit waves, out[3] = total
+ * bytes (all 0 when it wrote nothing). */
+void tkv_debug_wal_encode_last(uint64_t out[4]);
+/* tkv_wal_encode_device stamps records of record_len <= 240 inside its emit pass unless this is 0:
+ * then every record is stamped by the read-back route (kept so one process can run both routes on the
+ * same inputs). Returns the previous setting. Default 1. */
+int tkv_debug_set_wal_encode_fused(int enable);
 
 
 #ifdef __cplusplus

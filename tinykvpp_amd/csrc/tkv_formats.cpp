@@ -382,6 +382,137 @@ int tkv_wal_stamp(uint8_t* h_buf, const uint64_t* h_offsets, const uint32_t* h_s
   return TKV_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// ---- WAL group-commit encode (wal.cpp:19-61 for a batch) ---------------------------------------------
+struct EncodeIn {
+  const std::uint8_t* keys;
+  const std::uint64_t* key_off;
+  const std::uint32_t* key_len;
+  const std::uint8_t* vals;
+  const std::uint64_t* val_off;
+  const std::uint32_t* val_len;
+  const std::uint8_t* op;
+  const std::uint8_t* tomb;
+  const std::uint64_t* seq;
+  std::uint64_t first_seq;
+  std::uint64_t n;
+};
+
+// The argument checks both entry points share (n >= 1).
+int encode_check(const EncodeIn& in, const std::uint64_t* img_size) {
+  if (in.n > 0xFFFFFFFFull) return set_error(TKV_INVALID_ARGUMENT, "WAL encode: more than 2^32 - 1 records");
+  if (!ptr_ok(in.keys) || !ptr_ok(in.key_off) || !ptr_ok(in.key_len) || !ptr_ok(img_size) ||
+      (ptr_ok(in.val_len) && (!ptr_ok(in.vals) || !ptr_ok(in.val_off))))
+    return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  return TKV_OK;
+}
+
+// Record start offsets (n + 1 entries, the last one the total) of a host batch; TKV_INVALID_ARGUMENT when
+// a record_len does not fit u32 (no source byte is read).
+int encode_offsets(const EncodeIn& in, std::vector<std::uint64_t>& off) {
+  off.resize(in.n + 1);
+  std::uint64_t run = 0;
+  for (std::uint64_t i = 0; i < in.n; ++i) {
+    const std::uint64_t rl = 18ull + in.key_len[i] + (in.val_len ? in.val_len[i] : 0u);
+    if (rl > 0xFFFFFFFFull) return set_error(TKV_INVALID_ARGUMENT, "WAL encode: 18 + key_len + val_len does not fit u32");
+    off[i] = run;
+    run += rl + 8;
+  }
+  off[in.n] = run;
+  return TKV_OK;
+}
+
+// Records laid out at img + off[i] with their CRC fields zero (wal.cpp:27-52), on host threads.
+void encode_layout(const EncodeIn& in, const std::vector<std::uint64_t>& off, std::uint8_t* img) {
+  parallel_for(in.n, [&](std::uint64_t i) {
+    std::uint8_t* r = img + off[i];
+    const std::uint32_t kl = in.key_len[i], vl = in.val_len ? in.val_len[i] : 0u;
+    const std::uint32_t rl = 18u + kl + vl, zero = 0;
+    const std::uint64_t seq = in.seq ? in.seq[i] : in.first_seq + i;
+    std::memcpy(r, &rl, 4);
+    std::memcpy(r + 4, &zero, 4);
+    r[8] = in.op ? in.op[i] : 0;
+    for (int b = 0; b < 8; ++b) r[9 + b] = static_cast<std::uint8_t>(seq >> (8 * b));
+    r[17] = in.tomb && in.tomb[i] ? 1 : 0;
+    for (int b = 0; b < 4; ++b) r[18 + b] = static_cast<std::uint8_t>(kl >> (8 * b));
+    for (int b = 0; b < 4; ++b) r[22 + b] = static_cast<std::uint8_t>(vl >> (8 * b));
+    if (kl) std::memcpy(r + kWalMeta, in.keys + in.key_off[i], kl);
+    if (vl) std::memcpy(r + kWalMeta + kl, in.vals + in.val_off[i], vl);
+  });
+}
+
+// Checks, sizes and the layout of a host batch; *laid is set when the records were written.
+int encode_host_layout(const EncodeIn& in, std::uint8_t* h_img, std::uint64_t cap, std::uint64_t* img_size,
+                       std::vector<std::uint64_t>& off, bool* laid) {
+  *laid = false;
+  if (in.n == 0) {
+    if (ptr_ok(img_size)) *img_size = 0;
+    return TKV_OK;
+  }
+  if (int rc = encode_check(in, img_size)) return rc;
+  if (int rc = encode_offsets(in, off)) return rc;
+  *img_size = off[in.n];
+  if (off[in.n] > cap) return set_error(TKV_BUFFER_OVERFLOW, "WAL encode: the image does not fit cap");
+  if (!ptr_ok(h_img)) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  encode_layout(in, off, h_img);
+  *laid = true;
+  return TKV_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tkv_wal_encode_device(const uint8_t* d_keys, const uint64_t* d_key_off, const uint32_t* d_key_len,
+                          const uint8_t* d_vals, const uint64_t* d_val_off, const uint32_t* d_val_len, const uint8_t* d_op,
+                          const uint8_t* d_tomb, const uint64_t* d_seq, uint64_t first_seq, uint64_t n, uint8_t* d_img,
+                          uint64_t cap, uint64_t* d_rec_off, uint32_t* d_crc, uint64_t* img_size, void* stream) {
+  if (n == 0) {
+    if (ptr_ok(img_size)) *img_size = 0;
+    return TKV_OK;
+  }
+  const EncodeIn in{d_keys, d_key_off, d_key_len, d_vals, d_val_off, d_val_len, d_op, d_tomb, d_seq, first_seq, n};
+  if (int rc = encode_check(in, img_size)) return rc;
+  if (cap && !ptr_ok(d_img)) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  return wal_encode_device_impl(d_keys, d_key_off, d_key_len, d_vals, d_val_off, d_val_len, d_op, d_tomb, d_seq, first_seq,
+                                n, d_img, cap, d_rec_off, d_crc, img_size, static_cast<hipStream_t>(stream));
+}
+
+int tkv_wal_encode(const uint8_t* h_keys, const uint64_t* h_key_off, const uint32_t* h_key_len, const uint8_t* h_vals,
+                   const uint64_t* h_val_off, const uint32_t* h_val_len, const uint8_t* h_op, const uint8_t* h_tomb,
+                   const uint64_t* h_seq, uint64_t first_seq, uint64_t n, uint8_t* h_img, uint64_t cap,
+                   uint64_t* h_rec_off, uint32_t* h_crc, uint64_t* img_size) {
+  const EncodeIn in{h_keys, h_key_off, h_key_len, h_vals, h_val_off, h_val_len, h_op, h_tomb, h_seq, first_seq, n};
+  std::vector<std::uint64_t> off;
+  bool laid = false;
+  if (int rc = encode_host_layout(in, h_img, cap, img_size, off, &laid)) return rc;
+  if (!laid) return TKV_OK;
+  // the stamp of tkv_wal_stamp: CRC over [8, size) of every record on the GPU, then the fields (wal.cpp:54-58)
+  std::vector<std::uint64_t> poff(n);
+  std::vector<std::uint32_t> len(n), crc(n);
+  for (std::uint64_t i = 0; i < n; ++i) {
+    poff[i] = off[i] + 8;
+    len[i] = static_cast<std::uint32_t>(off[i + 1] - off[i] - 8);
+  }
+  if (int rc = batch_host_impl(kAlgoCrc32, h_img, poff.data(), len.data(), nullptr, crc.data(), n)) return rc;
+  parallel_for(n, [&](std::uint64_t i) { std::memcpy(h_img + off[i] + 4, &crc[i], 4); });
+  if (ptr_ok(h_rec_off)) std::memcpy(h_rec_off, off.data(), n * sizeof(std::uint64_t));
+  if (ptr_ok(h_crc)) std::memcpy(h_crc, crc.data(), n * sizeof(std::uint32_t));
+  return TKV_OK;
+}
+
+size_t tkv_debug_wal_encode_layout(const uint8_t* h_keys, const uint64_t* h_key_off, const uint32_t* h_key_len,
+                                   const uint8_t* h_vals, const uint64_t* h_val_off, const uint32_t* h_val_len,
+                                   const uint8_t* h_op, const uint8_t* h_tomb, const uint64_t* h_seq, uint64_t first_seq,
+                                   uint64_t n, uint8_t* h_img, uint64_t cap, uint64_t* img_size) {
+  const EncodeIn in{h_keys, h_key_off, h_key_len, h_vals, h_val_off, h_val_len, h_op, h_tomb, h_seq, first_seq, n};
+  std::vector<std::uint64_t> off;
+  bool laid = false;
+  if (encode_host_layout(in, h_img, cap, img_size, off, &laid) != TKV_OK || !laid) return 0;
+  return static_cast<size_t>(n);
+}
+
 
 int tkv_sst_stamp_blocks(uint8_t* h_file, const uint64_t* h_offsets, const uint64_t* h_sizes, uint64_t n) {
   if (n == 0) return TKV_OK;

@@ -39,4 +39,15 @@ int wal_index_host_image_impl(const std::uint8_t* h_wal, std::uint64_t size, std
                               std::uint64_t* n_good, std::uint64_t* stop_offset, std::uint64_t* max_sequence,
                               bool* needs_host_walk);
 
+// WAL group-commit encode on `st` (tkv_wal_encode.hip; synchronous): the size scan, the host's
+// overflow / invalid decision from its pinned result, then the emit into [d_img, d_img + total) with the
+// CRC of every record of record_len <= 240 folded in the same pass and the longer ones stamped by one
+// CRC batch over the written image. Arguments and results are tkv_wal_encode_device's (n >= 1 and the
+// required pointers checked by the caller).
+int wal_encode_device_impl(const std::uint8_t* d_keys, const std::uint64_t* d_key_off, const std::uint32_t* d_key_len,
+                           const std::uint8_t* d_vals, const std::uint64_t* d_val_off, const std::uint32_t* d_val_len,
+                           const std::uint8_t* d_op, const std::uint8_t* d_tomb, const std::uint64_t* d_seq,
+                           std::uint64_t first_seq, std::uint64_t n, std::uint8_t* d_img, std::uint64_t cap,
+                           std::uint64_t* d_rec_off, std::uint32_t* d_crc, std::uint64_t* img_size, hipStream_t st);
+
 }  // namespace tkv

@@ -1,0 +1,707 @@
+// WAL group-commit encode on the device: wal_entry::encode
+// (/root/reference/src/engine/wal.cpp:19-61) for a whole put batch held as key / value arenas with
+// per-record offsets and lengths. Record i is
+//   u32 record_len | u32 crc32 | u8 op | u64 seq | u8 tombstone | u32 key_len | u32 val_len | key | value
+// (little-endian, packed), record_len = 18 + key_len + val_len, crc32 = CRC-32 of bytes [8, 8 + record_len),
+// and the records lie back to back in batch order.
+//
+// enc_scan / enc_add: record sizes and their u64 exclusive prefix scan over n, kScanBlock records per
+// workgroup (DPP prefix per wave, wave totals through LDS), the block sums scanned by the next level,
+// up to kScanLevels levels. The host reads {total, overflow flag, long records} from a pinned block
+// and decides overflow / invalid before anything is written for the caller.
+// enc_finish: the final offsets, the caller's rec_off, for every emit tile the record that holds its
+// first byte and the last record that starts in it (so no emit wave searches the offsets) and the list
+// of records stamped by read-back.
+// enc_emit: the image cut into tiles of kEncTile bytes, tile t, t + W, ... to wave t of W. A tile's record
+// range is read two tiles ahead and its first 64 records' inputs one tile ahead. One wave builds its tile in an LDS window:
+// headers and short keys / values one record per lane, long spans by the whole wave 16 bytes per lane
+// (two source granules and v_alignbyte take the source / destination misalignment out), then folds
+// the CRC of every record of record_len <= kLaneFold from the window (fold_raw, the sweep's lane
+// fold), writes it into the window and stores the tile with coalesced 16-byte stores; the granules it
+// shares with a neighbouring tile or with bytes outside the image go out bytewise, nothing is read
+// back. The window reaches kEncOver bytes past the tile and kEncPre in front of it, so such a record
+// lies wholly in the window of every tile that holds a byte of its CRC field, wherever it starts.
+// Longer records are copied piecewise by the tiles they cross with a zero CRC field; one CRC batch
+// over the written image (batch_device_impl) and enc_stamp fill their fields afterwards, in stream
+// order.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstdint>
+#include <mutex>
+
+#include "tkv_crc32.h"
+#include "tkv_crc32_device.h"
+#include "tkv_engine.h"
+#include "tkv_wal_device.h"
+#include "tkv_wal_fold.h"
+
+namespace tkv {
+namespace {
+
+constexpr std::uint64_t kWalMeta = 26;        // wal.hpp:21-27 kMetadataSize
+constexpr std::uint32_t kEncTile = 4096;      // image bytes per emit tile
+constexpr std::uint32_t kEncPre = 16;         // window bytes in front of the tile's 16-byte granule
+constexpr std::uint32_t kEncOver = 288;       // window bytes past the tile
+constexpr std::uint32_t kEncWin = kEncPre + 16 + kEncTile + kEncOver;
+constexpr unsigned kEncWaves = 16;            // waves per workgroup: the 64 KiB tables + 16 windows of LDS
+constexpr unsigned kEncThreads = 64 * kEncWaves;
+constexpr std::uint32_t kShortSpan = 64;      // keys / values up to this long are copied by their record's lane
+constexpr unsigned kScanThreads = 256;
+constexpr unsigned kScanItems = 4;            // consecutive records per thread
+constexpr std::uint64_t kScanBlock = kScanThreads * kScanItems;  // records per workgroup of the size scan
+constexpr int kScanLevels = 4;                // kScanBlock^4 >= 2^32 records
+constexpr unsigned kEncHres = 4;              // words of the pinned result block
+enum : int { kCntFlag = 0, kCntLong, kCntCursor, kCntWords = 4 };
+// a folded record that starts in the tile's last byte ends, and fold_raw's frozen steps read, inside the window
+static_assert(kEncPre + 15 + kEncTile - 1 + 8 + kLaneFold + 12 <= kEncWin, "window");
+static_assert(kEncPre >= 8 + 8, "a record whose CRC field reaches into the tile starts in the window, fold_raw's s >= 8");
+static_assert(kEncTile % 16 == 0 && kEncWin % 16 == 0, "16-byte granules");
+static_assert(kLdsSliceWords * 2 + kEncWaves * kEncWin + 4 * (kLaneFold + 1) <= 163840, "LDS");
+
+struct EncArgs {
+  const std::uint8_t* keys;
+  const std::uint64_t* key_off;
+  const std::uint32_t* key_len;
+  const std::uint8_t* vals;
+  const std::uint64_t* val_off;
+  const std::uint32_t* val_len;  // nullable: every value empty
+  const std::uint8_t* op;        // nullable: 0
+  const std::uint8_t* tomb;      // nullable: 0
+  const std::uint64_t* seq;      // nullable: first_seq + i
+  std::uint64_t first_seq;
+  std::uint64_t n;
+  std::uint8_t* img;
+  std::uint64_t total;
+  std::uint64_t* off;            // scratch: record start offsets
+  std::uint64_t* rec_off;        // nullable: the caller's copy
+  std::uint32_t* crc;            // nullable: the caller's stamped CRCs
+  std::uint32_t* tile_first;     // per tile, two words: the record that holds its first byte, the last one that starts in it
+  std::uint64_t ntiles;
+  std::uint64_t* l_off;          // records stamped by read-back: offset of byte 8, record_len, index, CRC
+  std::uint32_t* l_len;
+  std::uint32_t* l_idx;
+  std::uint32_t* l_crc;
+  unsigned long long* cnt;       // kCntWords device words
+  std::uint32_t fused;
+  std::uint32_t nwaves;
+  const DeviceTables* tabs;
+};
+
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// ---- size scan --------------------------------------------------------------------------------------
+
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ std::uint64_t dpp_add64(std::uint64_t x) {
+  const std::uint32_t lo = static_cast<std::uint32_t>(
+      __builtin_amdgcn_update_dpp(0, static_cast<int>(static_cast<std::uint32_t>(x)), CTRL, ROW_MASK, 0xF, false));
+  const std::uint32_t hi = static_cast<std::uint32_t>(
+      __builtin_amdgcn_update_dpp(0, static_cast<int>(static_cast<std::uint32_t>(x >> 32)), CTRL, ROW_MASK, 0xF, false));
+  return x + ((static_cast<std::uint64_t>(hi) << 32) | lo);
+}
+// dev::lane_prefix over u64 values.
+__device__ __forceinline__ std::uint64_t lane_prefix64(std::uint64_t v, std::uint64_t* total) {
+  std::uint64_t x = v;
+  x = dpp_add64<0x111, 0xF>(x);  // row_shr:1
+  x = dpp_add64<0x112, 0xF>(x);  // row_shr:2
+  x = dpp_add64<0x114, 0xF>(x);  // row_shr:4
+  x = dpp_add64<0x118, 0xF>(x);  // row_shr:8
+  x = dpp_add64<0x142, 0xA>(x);  // row_bcast:15 into rows 1 and 3
+  x = dpp_add64<0x143, 0xC>(x);  // row_bcast:31 into rows 2 and 3
+  *total = dev::readlane64(x, 63);
+  return x - v;
+}
+__device__ __forceinline__ std::uint64_t block_prefix64(std::uint64_t v, std::uint64_t* total) {
+  __shared__ std::uint64_t wsum[kScanThreads / 64];
+  std::uint64_t wt;
+  const std::uint64_t pre = lane_prefix64(v, &wt);
+  const std::uint32_t wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 0) wsum[wv] = wt;
+  __syncthreads();
+  std::uint64_t before = 0, all = 0;
+#pragma unroll
+  for (std::uint32_t k = 0; k < kScanThreads / 64; ++k) {
+    before += k < wv ? wsum[k] : 0u;
+    all += wsum[k];
+  }
+  *total = all;
+  return before + pre;
+}
+
+__device__ __forceinline__ std::uint64_t rec_len64(const EncArgs& a, std::uint64_t i) {
+  return 18ull + a.key_len[i] + (a.val_len ? a.val_len[i] : 0u);
+}
+
+// Exclusive prefix within each block of kScanBlock entries, the block's sum to bsum[block]. LEVEL0: the
+// entries are the record sizes (written to a.off), the u32 overflow flag and the count of records the
+// emit pass does not stamp; else arr[0, m) in place.
+template <bool LEVEL0>
+__global__ __launch_bounds__(kScanThreads) void enc_scan(EncArgs a, std::uint64_t* arr, std::uint64_t m, std::uint64_t* bsum) {
+  const std::uint64_t i0 = blockIdx.x * kScanBlock + threadIdx.x * kScanItems;
+  std::uint64_t v[kScanItems];
+  std::uint64_t s = 0;
+  std::uint32_t nlong = 0, bad = 0;
+#pragma unroll
+  for (unsigned k = 0; k < kScanItems; ++k) {
+    const std::uint64_t i = i0 + k;
+    v[k] = 0;
+    if (i < m) {
+      if constexpr (LEVEL0) {
+        const std::uint64_t rl = rec_len64(a, i);
+        v[k] = rl + 8u;
+        bad |= rl > 0xFFFFFFFFull ? 1u : 0u;
+        nlong += (rl > kLaneFold || !a.fused) ? 1u : 0u;
+      } else {
+        v[k] = arr[i];
+      }
+    }
+    s += v[k];
+  }
+  std::uint64_t total;
+  std::uint64_t run = block_prefix64(s, &total);
+#pragma unroll
+  for (unsigned k = 0; k < kScanItems; ++k) {
+    const std::uint64_t i = i0 + k;
+    if (i < m) arr[i] = run;
+    run += v[k];
+  }
+  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+  if constexpr (LEVEL0) {
+    if (bad) atomicOr(&a.cnt[kCntFlag], 1ull);
+    if (nlong) atomicAdd(&a.cnt[kCntLong], static_cast<unsigned long long>(nlong));
+  }
+}
+
+__global__ __launch_bounds__(kScanThreads) void enc_add(std::uint64_t* arr, std::uint64_t m, const std::uint64_t* base) {
+  const std::uint64_t i = blockIdx.x * static_cast<std::uint64_t>(kScanThreads) + threadIdx.x;
+  if (i < m) arr[i] += base[i / kScanBlock];
+}
+
+__global__ void enc_publish(const std::uint64_t* top, const unsigned long long* cnt, std::uint64_t* h) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    h[0] = *top;
+    h[1] = cnt[kCntFlag];
+    h[2] = cnt[kCntLong];
+    h[3] = 1;
+  }
+}
+
+__global__ __launch_bounds__(kScanThreads) void enc_finish(EncArgs a, const std::uint64_t* base) {
+  const std::uint64_t i = blockIdx.x * static_cast<std::uint64_t>(kScanThreads) + threadIdx.x;
+  if (i >= a.n) return;
+  const std::uint64_t o = a.off[i] + (base ? base[i / kScanBlock] : 0u);
+  a.off[i] = o;
+  if (a.rec_off) a.rec_off[i] = o;
+  const std::uint64_t rl = rec_len64(a, i);
+  const std::uint64_t e = o + rl + 8u;
+  for (std::uint64_t t = o / kEncTile; t * kEncTile < e; ++t) {  // one writer per word: records tile the image
+    if (o <= t * kEncTile) a.tile_first[2u * t] = static_cast<std::uint32_t>(i);
+    if (e >= (t + 1u) * kEncTile || i + 1u == a.n) a.tile_first[2u * t + 1u] = static_cast<std::uint32_t>(i);
+  }
+  if (rl > kLaneFold || !a.fused) {
+    const unsigned long long k = atomicAdd(&a.cnt[kCntCursor], 1ull);
+    a.l_off[k] = o + 8u;
+    a.l_len[k] = static_cast<std::uint32_t>(rl);
+    a.l_idx[k] = static_cast<std::uint32_t>(i);
+  }
+}
+
+__global__ __launch_bounds__(kScanThreads) void enc_stamp(EncArgs a, std::uint64_t nlong) {
+  const std::uint64_t k = blockIdx.x * static_cast<std::uint64_t>(kScanThreads) + threadIdx.x;
+  if (k >= nlong) return;
+  const std::uint32_t c = a.l_crc[k];
+  std::uint8_t* p = a.img + (a.l_off[k] - 4u);
+  p[0] = static_cast<std::uint8_t>(c);
+  p[1] = static_cast<std::uint8_t>(c >> 8);
+  p[2] = static_cast<std::uint8_t>(c >> 16);
+  p[3] = static_cast<std::uint8_t>(c >> 24);
+  if (a.crc) a.crc[a.l_idx[k]] = c;
+}
+
+// ---- emit -------------------------------------------------------------------------------------------
+
+// The aligned dword / granule at address p when it holds a byte of [s, e), else zero (no load leaves
+// the source span rounded out to its granules).
+// (Global address space: a generic load could alias the LDS window, and every load of a copy would then
+// wait for the window stores in front of it.)
+using GlobalU32 = const __attribute__((address_space(1))) std::uint32_t*;
+typedef std::uint32_t U32x4 __attribute__((ext_vector_type(4)));
+using GlobalU128 = const __attribute__((address_space(1))) U32x4*;
+__device__ __forceinline__ std::uint32_t ld4(std::uintptr_t p, std::uintptr_t s, std::uintptr_t e) {
+  return (p + 4u > s && p < e) ? *reinterpret_cast<GlobalU32>(p) : 0u;
+}
+__device__ __forceinline__ uint4 ld16(std::uintptr_t p, std::uintptr_t s, std::uintptr_t e) {
+  U32x4 v = {0u, 0u, 0u, 0u};
+  if (p + 16u > s && p < e) v = *reinterpret_cast<GlobalU128>(p);
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// The bytes of v (window bytes [q, q + 4)) that lie in [d, e).
+__device__ __forceinline__ void put4(std::uint8_t* win, std::uint32_t q, std::uint32_t v, std::uint32_t d, std::uint32_t e) {
+  if (q >= d && q + 4u <= e) {
+    *reinterpret_cast<std::uint32_t*>(win + q) = v;
+  } else {
+#pragma unroll
+    for (std::uint32_t b = 0; b < 4u; ++b)
+      if (q + b >= d && q + b < e) win[q + b] = static_cast<std::uint8_t>(v >> (8u * b));
+  }
+}
+
+// One lane's copy of len source bytes at src to window bytes [d, d + len) (nothing when on is false):
+// aligned source dwords, each window dword from two of them (v_alignbyte).
+struct LaneSpan {
+  std::uint32_t q, d, e, sh;      // next window dword, the span's window bytes, source misalignment
+  std::uintptr_t sa, s0, se;      // source address of window dword q rounded down, the source bytes
+};
+__device__ __forceinline__ LaneSpan lane_span(std::uint32_t d, std::uintptr_t src, std::uint32_t len, bool on) {
+  LaneSpan s{};
+  if (on) {
+    s.q = d & ~3u;
+    s.d = d;
+    s.e = d + len;
+    const std::uintptr_t sp = src - (d - s.q);  // source address of window byte q
+    s.sh = static_cast<std::uint32_t>(sp & 3u);
+    s.sa = sp & ~static_cast<std::uintptr_t>(3);
+    s.s0 = src;
+    s.se = src + len;
+  }
+  return s;
+}
+// Two such copies side by side (a record's key and value), four window dwords of each per step with the
+// step's ten loads issued together.
+__device__ __forceinline__ void lane_copy2(std::uint8_t* win, LaneSpan a, LaneSpan b) {
+  while (a.q < a.e || b.q < b.e) {
+    std::uint32_t wa[5], wb[5];
+#pragma unroll
+    for (std::uint32_t k = 0; k < 5u; ++k) {
+      wa[k] = ld4(a.sa + 4u * k, a.s0, a.se);
+      wb[k] = ld4(b.sa + 4u * k, b.s0, b.se);
+    }
+#pragma unroll
+    for (std::uint32_t k = 0; k < 4u; ++k) {
+      put4(win, a.q + 4u * k, __builtin_amdgcn_alignbyte(wa[k + 1u], wa[k], a.sh), a.d, a.e);
+      put4(win, b.q + 4u * k, __builtin_amdgcn_alignbyte(wb[k + 1u], wb[k], b.sh), b.d, b.e);
+    }
+    a.q += 16u;
+    a.sa += 16u;
+    b.q += 16u;
+    b.sa += 16u;
+  }
+}
+
+// The same by the whole wave (wave-uniform arguments), a 16-byte window granule per lane: the two
+// source granules that hold its bytes, shifted by the wave-uniform misalignment. A span covers at most
+// kWaveSteps steps of 64 granules (it lies in the window); their loads are issued together.
+constexpr std::uint32_t kWaveSteps = (kEncWin + 1023u) / 1024u;
+__device__ __forceinline__ void wave_copy(std::uint8_t* win, std::uint32_t d, std::uintptr_t src, std::uint32_t len, std::uint32_t lane) {
+  const std::uint32_t e = d + len;
+  const std::uint32_t g0 = d & ~15u;
+  const std::uintptr_t sp0 = src - (d - g0);  // source address of window byte g0
+  const std::uint32_t r = static_cast<std::uint32_t>(sp0 & 15u);
+  const std::uint32_t k = r >> 2, sh = r & 3u;
+  const std::uintptr_t se = src + len;
+  uint4 As[kWaveSteps], Bs[kWaveSteps];
+#pragma unroll
+  for (std::uint32_t it = 0; it < kWaveSteps; ++it) {
+    const std::uint32_t g = g0 + 16u * lane + 1024u * it;
+    const std::uintptr_t sa = (sp0 + (g - g0)) & ~static_cast<std::uintptr_t>(15);
+    // (past the span's end sa >= se: nothing is loaded)
+    As[it] = ld16(sa, src, se);
+    Bs[it] = ld16(sa + 16u, src, se);
+  }
+#pragma unroll
+  for (std::uint32_t it = 0; it < kWaveSteps; ++it) {
+    const std::uint32_t g = g0 + 16u * lane + 1024u * it;
+    if (g >= e) break;
+    const uint4 A = As[it], B = Bs[it];
+    uint4 v;
+    switch (k) {
+      case 0:
+        v = make_uint4(__builtin_amdgcn_alignbyte(A.y, A.x, sh), __builtin_amdgcn_alignbyte(A.z, A.y, sh),
+                       __builtin_amdgcn_alignbyte(A.w, A.z, sh), __builtin_amdgcn_alignbyte(B.x, A.w, sh));
+        break;
+      case 1:
+        v = make_uint4(__builtin_amdgcn_alignbyte(A.z, A.y, sh), __builtin_amdgcn_alignbyte(A.w, A.z, sh),
+                       __builtin_amdgcn_alignbyte(B.x, A.w, sh), __builtin_amdgcn_alignbyte(B.y, B.x, sh));
+        break;
+      case 2:
+        v = make_uint4(__builtin_amdgcn_alignbyte(A.w, A.z, sh), __builtin_amdgcn_alignbyte(B.x, A.w, sh),
+                       __builtin_amdgcn_alignbyte(B.y, B.x, sh), __builtin_amdgcn_alignbyte(B.z, B.y, sh));
+        break;
+      default:
+        v = make_uint4(__builtin_amdgcn_alignbyte(B.x, A.w, sh), __builtin_amdgcn_alignbyte(B.y, B.x, sh),
+                       __builtin_amdgcn_alignbyte(B.z, B.y, sh), __builtin_amdgcn_alignbyte(B.w, B.z, sh));
+        break;
+    }
+    if (g >= d && g + 16u <= e) {
+      *reinterpret_cast<uint4*>(win + g) = v;
+    } else {
+      put4(win, g, v.x, d, e);
+      put4(win, g + 4u, v.y, d, e);
+      put4(win, g + 8u, v.z, d, e);
+      put4(win, g + 12u, v.w, d, e);
+    }
+  }
+}
+
+// A source span of len bytes at src that lies at image bytes [sx, sx + len), cut to the image bytes
+// [clo, chi) this wave lays out: its window offset (wb = window offset of image byte ts), source
+// address and length (0 when nothing is left).
+struct Span {
+  std::uint32_t d, len;
+  std::uintptr_t src;
+};
+__device__ __forceinline__ Span clip_span(std::uintptr_t src, std::uint64_t len, std::uint64_t sx, std::uint64_t clo,
+                                          std::uint64_t chi, std::uint64_t ts, std::uint32_t wb) {
+  const std::uint64_t c0 = sx > clo ? sx : clo;
+  const std::uint64_t c1 = sx + len < chi ? sx + len : chi;
+  Span s{0u, 0u, src};
+  if (c1 > c0) {
+    s.len = static_cast<std::uint32_t>(c1 - c0);
+    s.src = src + static_cast<std::uintptr_t>(c0 - sx);
+    s.d = wb + static_cast<std::uint32_t>(static_cast<std::int32_t>(static_cast<std::int64_t>(c0 - ts)));
+  }
+  return s;
+}
+
+// Long spans of the round's records, one after the other by the whole wave.
+__device__ __forceinline__ void wave_spans(std::uint8_t* win, const Span& s, std::uint32_t lane) {
+  unsigned long long m = __ballot(s.len > kShortSpan);
+  while (m) {
+    const std::uint32_t l = static_cast<std::uint32_t>(__ffsll(m)) - 1u;
+    m &= m - 1ull;
+    const std::uint32_t d = static_cast<std::uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(s.d), static_cast<int>(l)));
+    const std::uint32_t len = static_cast<std::uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(s.len), static_cast<int>(l)));
+    const std::uintptr_t src = static_cast<std::uintptr_t>(dev::readlane64(static_cast<std::uint64_t>(s.src), l));
+    wave_copy(win, d, src, len, lane);
+  }
+}
+
+// A record's inputs as the emit pass reads them, one record per lane.
+struct Rec {
+  std::uint64_t ro, seq, ko, vo;
+  std::uint32_t kl, vl, op, tomb;
+};
+__device__ __forceinline__ Rec load_rec(const EncArgs& a, std::uint64_t i, bool act) {
+  Rec r{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  if (act) {
+    r.ro = a.off[i];
+    r.kl = a.key_len[i];
+    r.ko = a.key_off[i];
+    if (a.val_len) {
+      r.vl = a.val_len[i];
+      r.vo = a.val_off[i];
+    }
+    r.op = a.op ? a.op[i] : 0u;
+    r.tomb = a.tomb ? (a.tomb[i] ? 1u : 0u) : 0u;
+    r.seq = a.seq ? a.seq[i] : a.first_seq + i;
+  }
+  return r;
+}
+// The records of tile t: [x, y] (enc_finish).
+__device__ __forceinline__ uint2 tile_head(const EncArgs& a, std::uint64_t t) {
+  return *reinterpret_cast<const uint2*>(a.tile_first + 2u * t);
+}
+
+// One tile. head and r0 (the tile's first 64 records, one per lane) were loaded a tile ahead.
+__device__ __forceinline__ void emit_tile(const EncArgs& a, std::uint8_t* win, const std::uint32_t* tab, const std::uint32_t* inj,
+                                          const dev::LaneConstX& kc, std::uint64_t t, uint2 head, const Rec& r0,
+                                          std::uint32_t lane) {
+  const std::uint64_t ts = t * kEncTile;
+  const std::uint64_t te = ts + kEncTile < a.total ? ts + kEncTile : a.total;
+  const std::uint64_t first = head.x, last = head.y;
+  std::uint8_t* const dst = a.img + ts;
+  const std::uint32_t o = static_cast<std::uint32_t>(reinterpret_cast<std::uintptr_t>(dst) & 15u);
+  const std::uint32_t wb = kEncPre + o;  // window offset of image byte ts: window granules are the image's
+  for (std::uint64_t rb = first; rb <= last; rb += 64u) {
+    const std::uint64_t i = rb + lane;
+    const bool act = i <= last;
+    const Rec r = rb == first ? r0 : load_rec(a, i, act);
+    const std::uint64_t ro = act ? r.ro : ts, seq = r.seq, ko = r.ko, vo = r.vo;
+    const std::uint32_t kl = r.kl, vl = r.vl, op = r.op, tomb = r.tomb;
+    const std::uint32_t rl = 18u + kl + vl;  // fits: the host checked the scan's flag
+    const std::uint64_t size = static_cast<std::uint64_t>(rl) + 8u;
+    // folded here: short, and a byte of its CRC field lies in the tile (it starts before te)
+    const bool fold = act && a.fused && rl <= kLaneFold && ro + 8u > ts;
+    const std::uint64_t clo = fold ? ro : (ro > ts ? ro : ts);
+    const std::uint64_t chi = fold ? ro + size : (ro + size < te ? ro + size : te);
+    // window offset of the record's byte 0 (meaningful when a header byte is laid out)
+    const std::uint32_t hw = wb + static_cast<std::uint32_t>(static_cast<std::int32_t>(static_cast<std::int64_t>(ro - ts)));
+    if (act) {
+      const std::uint32_t hb0 = clo > ro ? static_cast<std::uint32_t>(clo - ro < kWalMeta ? clo - ro : kWalMeta) : 0u;
+      const std::uint32_t hb1 = static_cast<std::uint32_t>(chi - ro < kWalMeta ? chi - ro : kWalMeta);
+      if (hb0 < hb1) {
+        const std::uint32_t h[7] = {rl,
+                                    0u,
+                                    op | (static_cast<std::uint32_t>(seq) << 8),
+                                    static_cast<std::uint32_t>(seq >> 24),
+                                    static_cast<std::uint32_t>(seq >> 56) | (tomb << 8) | (kl << 16),
+                                    (kl >> 16) | (vl << 16),
+                                    vl >> 16};
+#pragma unroll
+        for (std::uint32_t b = 0; b < kWalMeta; ++b)
+          if (b >= hb0 && b < hb1) win[hw + b] = static_cast<std::uint8_t>(h[b >> 2] >> (8u * (b & 3u)));
+      }
+    }
+    Span ks{0u, 0u, 0}, vs{0u, 0u, 0};
+    if (act) {
+      ks = clip_span(reinterpret_cast<std::uintptr_t>(a.keys) + ko, kl, ro + kWalMeta, clo, chi, ts, wb);
+      if (vl) vs = clip_span(reinterpret_cast<std::uintptr_t>(a.vals) + vo, vl, ro + kWalMeta + kl, clo, chi, ts, wb);
+    }
+    lane_copy2(win, lane_span(ks.d, ks.src, ks.len, ks.len != 0u && ks.len <= kShortSpan),
+               lane_span(vs.d, vs.src, vs.len, vs.len != 0u && vs.len <= kShortSpan));
+    wave_spans(win, ks, lane);
+    wave_spans(win, vs, lane);
+    wave_sync();
+    // the lane fold (fold_raw plus the initial register's term), its CRC into the window's field
+    const std::uint32_t L = fold ? rl : 0u;
+    const std::uint32_t c = fold_raw(win, tab, kc, fold ? hw + 8u : kEncPre, L) ^ inj[L] ^ 0xFFFFFFFFu;
+    if (fold) {
+#pragma unroll
+      for (std::uint32_t b = 0; b < 4u; ++b) win[hw + 4u + b] = static_cast<std::uint8_t>(c >> (8u * b));
+      if (ro >= ts && a.crc) a.crc[i] = c;
+    }
+  }
+  wave_sync();
+  // the tile out of the window: whole granules with 16-byte stores, the (at most two) granules shared
+  // with a neighbour or with bytes outside the image bytewise
+  const std::uint32_t len = static_cast<std::uint32_t>(te - ts);
+  const std::uint32_t ng = (o + len + 15u) >> 4;
+  std::uint8_t* const g0 = dst - o;
+  for (std::uint32_t j = lane; j < ng; j += 64u) {
+    const std::uint32_t lo = 16u * j, hi = lo + 16u;  // bytes from g0
+    const uint4 v = *reinterpret_cast<const uint4*>(win + kEncPre + lo);
+    if (lo >= o && hi <= o + len) {
+      *reinterpret_cast<uint4*>(g0 + lo) = v;
+    } else {
+      const std::uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (std::uint32_t b = 0; b < 16u; ++b)
+        if (lo + b >= o && lo + b < o + len) g0[lo + b] = static_cast<std::uint8_t>(w[b >> 2] >> (8u * (b & 3u)));
+    }
+  }
+  wave_sync();
+}
+
+__global__ __launch_bounds__(kEncThreads) void enc_emit(EncArgs a) {
+  // one block with the tables at LDS address 0, so a lookup's v_perm result is its address
+  __shared__ __attribute__((aligned(16))) std::uint8_t lds[kLdsSliceWords * 2 + kEncWaves * kEncWin + 4 * (kLaneFold + 1)];
+  std::uint32_t* tab = reinterpret_cast<std::uint32_t*>(lds);
+  std::uint32_t* inj = reinterpret_cast<std::uint32_t*>(lds + kLdsSliceWords * 2 + kEncWaves * kEncWin);  // Shift_L(0xFFFFFFFF)
+  dev::fill_lds_slicing16(a.tabs, tab);
+  for (std::uint32_t i = threadIdx.x; i <= kLaneFold; i += blockDim.x) inj[i] = a.tabs->init_shift[i];
+  __syncthreads();
+  const std::uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const std::uint32_t lane = threadIdx.x & 63u;
+  std::uint8_t* win = lds + kLdsSliceWords * 2 + wv * kEncWin;
+  const dev::LaneConstX kc = dev::lane_const16(lane);
+  // a tile's first and last record are read two tiles ahead and its first 64 records one tile ahead, so
+  // their latency lies under the tile in front
+  std::uint64_t t = blockIdx.x * kEncWaves + wv;
+  if (t >= a.ntiles) return;
+  uint2 h = tile_head(a, t);
+  Rec r0 = load_rec(a, h.x + lane, h.x + lane <= h.y);
+  uint2 hn = t + a.nwaves < a.ntiles ? tile_head(a, t + a.nwaves) : make_uint2(1u, 0u);
+  for (; t < a.ntiles; t += a.nwaves) {
+    const Rec rn = load_rec(a, static_cast<std::uint64_t>(hn.x) + lane, static_cast<std::uint64_t>(hn.x) + lane <= hn.y);
+    const uint2 hnn = t + 2ull * a.nwaves < a.ntiles ? tile_head(a, t + 2ull * a.nwaves) : make_uint2(1u, 0u);
+    emit_tile(a, win, tab, inj, kc, t, h, r0, lane);
+    h = hn;
+    r0 = rn;
+    hn = hnn;
+  }
+}
+
+// ---- host side --------------------------------------------------------------------------------------
+
+// Per-device scratch, grown by doubling and kept between calls (guarded by mu).
+struct EncScratch {
+  std::mutex mu;
+  std::uint64_t cap_off = 0, cap_sum = 0, cap_tile = 0, cap_long = 0;
+  void* off = nullptr;    // record offsets (u64)
+  void* sums = nullptr;   // block sums of every scan level (u64)
+  void* tiles = nullptr;  // first and last record of every tile (2 x u32)
+  void* lng = nullptr;    // read-back list: off (u64), len, idx, crc (u32)
+  unsigned long long* cnt = nullptr;
+  std::uint64_t* h_res = nullptr;   // pinned, kEncHres words
+  std::uint64_t* d_hres = nullptr;  // device view of h_res
+  int ncu = 0;
+  ~EncScratch() {
+    (void)hipFree(off);
+    (void)hipFree(sums);
+    (void)hipFree(tiles);
+    (void)hipFree(lng);
+    (void)hipFree(cnt);
+    (void)hipHostFree(h_res);
+  }
+};
+
+std::mutex g_enc_mu;
+EncScratch* g_enc[64] = {};
+std::atomic<int> g_enc_fused{1};
+// What the calling thread's last device encode did (tkv_debug_wal_encode_last).
+thread_local std::uint64_t g_enc_last[4] = {0, 0, 0, 0};
+
+#define ENC_HIP(call)                                                            \
+  do {                                                                           \
+    hipError_t e_ = (call);                                                      \
+    if (e_ != hipSuccess) return set_error(TKV_IO_ERROR, hipGetErrorString(e_)); \
+  } while (0)
+
+unsigned blocks(std::uint64_t n, std::uint64_t t) { return static_cast<unsigned>((n + t - 1) / t); }
+
+int grow(void** p, std::uint64_t* cap, std::uint64_t want, std::uint64_t unit) {
+  if (want <= *cap) return TKV_OK;
+  const std::uint64_t c = std::max<std::uint64_t>(want, 2 * *cap);
+  ENC_HIP(hipFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  ENC_HIP(hipMalloc(p, c * unit));
+  *cap = c;
+  return TKV_OK;
+}
+
+int scratch(EncScratch** out) {
+  int dev = 0;
+  ENC_HIP(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) return set_error(TKV_INVALID_ARGUMENT, "device index out of range");
+  EncScratch* sp;
+  {
+    std::lock_guard<std::mutex> lk(g_enc_mu);
+    if (!g_enc[dev]) g_enc[dev] = new EncScratch();
+    sp = g_enc[dev];
+  }
+  std::lock_guard<std::mutex> lk(sp->mu);
+  if (!sp->cnt) {
+    hipDeviceProp_t prop;
+    ENC_HIP(hipGetDeviceProperties(&prop, dev));
+    sp->ncu = prop.multiProcessorCount;
+    ENC_HIP(hipHostMalloc(reinterpret_cast<void**>(&sp->h_res), kEncHres * sizeof(std::uint64_t), hipHostMallocDefault));
+    ENC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&sp->d_hres), sp->h_res, 0));
+    ENC_HIP(hipMalloc(reinterpret_cast<void**>(&sp->cnt), kCntWords * sizeof(unsigned long long)));
+  }
+  *out = sp;
+  return TKV_OK;
+}
+
+int encode_locked(EncScratch& s, EncArgs a, std::uint64_t cap, std::uint64_t* img_size, hipStream_t st) {
+  // entries of the scan levels: level k + 1 holds the block sums of level k, the last one a single sum
+  std::uint64_t m[kScanLevels + 1];
+  int levels = 0;
+  m[0] = a.n;
+  while (m[levels] > 1u || levels == 0) {
+    m[levels + 1] = (m[levels] + kScanBlock - 1u) / kScanBlock;
+    ++levels;
+  }
+  std::uint64_t nsum = 0;
+  for (int k = 1; k <= levels; ++k) nsum += m[k];
+  if (int rc = grow(&s.off, &s.cap_off, a.n, 8)) return rc;
+  if (int rc = grow(&s.sums, &s.cap_sum, nsum, 8)) return rc;
+  a.off = static_cast<std::uint64_t*>(s.off);
+  a.cnt = s.cnt;
+  std::uint64_t* lv[kScanLevels + 1];
+  lv[0] = a.off;
+  lv[1] = static_cast<std::uint64_t*>(s.sums);
+  for (int k = 2; k <= levels; ++k) lv[k] = lv[k - 1] + m[k - 1];
+  ENC_HIP(hipMemsetAsync(s.cnt, 0, kCntWords * sizeof(unsigned long long), st));
+  s.h_res[3] = 0;
+  hipLaunchKernelGGL(enc_scan<true>, dim3(static_cast<unsigned>(m[1])), dim3(kScanThreads), 0, st, a, lv[0], m[0], lv[1]);
+  for (int k = 1; k < levels; ++k)
+    hipLaunchKernelGGL(enc_scan<false>, dim3(static_cast<unsigned>(m[k + 1])), dim3(kScanThreads), 0, st, a, lv[k], m[k], lv[k + 1]);
+  hipLaunchKernelGGL(enc_publish, dim3(1), dim3(64), 0, st, lv[levels], s.cnt, s.d_hres);
+  ENC_HIP(hipGetLastError());
+  ENC_HIP(hipStreamSynchronize(st));
+  if (s.h_res[3] != 1) return set_error(TKV_IO_ERROR, "WAL encode: the size scan left no result");
+  const std::uint64_t total = s.h_res[0], nlong = s.h_res[2];
+  if (s.h_res[1]) return set_error(TKV_INVALID_ARGUMENT, "WAL encode: 18 + key_len + val_len does not fit u32");
+  *img_size = total;
+  if (total > cap) return set_error(TKV_BUFFER_OVERFLOW, "WAL encode: the image does not fit cap");
+  if (!a.img) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  a.total = total;
+  a.ntiles = (total + kEncTile - 1u) / kEncTile;
+  if (int rc = grow(&s.tiles, &s.cap_tile, a.ntiles, 8)) return rc;
+  if (int rc = grow(&s.lng, &s.cap_long, nlong, 8 + 3 * 4)) return rc;
+  a.tile_first = static_cast<std::uint32_t*>(s.tiles);
+  a.l_off = static_cast<std::uint64_t*>(s.lng);
+  a.l_len = reinterpret_cast<std::uint32_t*>(a.l_off + s.cap_long);
+  a.l_idx = a.l_len + s.cap_long;
+  a.l_crc = a.l_idx + s.cap_long;
+  for (int k = levels - 2; k >= 1; --k)
+    hipLaunchKernelGGL(enc_add, dim3(blocks(m[k], kScanThreads)), dim3(kScanThreads), 0, st, lv[k], m[k], lv[k + 1]);
+  hipLaunchKernelGGL(enc_finish, dim3(blocks(a.n, kScanThreads)), dim3(kScanThreads), 0, st, a,
+                     levels > 1 ? lv[1] : static_cast<const std::uint64_t*>(nullptr));
+  const std::uint64_t want = (a.ntiles + kEncWaves - 1u) / kEncWaves;
+  const unsigned grid = static_cast<unsigned>(std::min<std::uint64_t>(want, static_cast<std::uint64_t>(std::max(1, s.ncu))));
+  a.nwaves = grid * kEncWaves;
+  hipLaunchKernelGGL(enc_emit, dim3(grid), dim3(kEncThreads), 0, st, a);
+  ENC_HIP(hipGetLastError());
+  if (nlong) {
+    if (int rc = batch_device_impl(kAlgoCrc32, a.img, a.l_off, a.l_len, nullptr, a.l_crc, nlong, st)) return rc;
+    hipLaunchKernelGGL(enc_stamp, dim3(blocks(nlong, kScanThreads)), dim3(kScanThreads), 0, st, a, nlong);
+    ENC_HIP(hipGetLastError());
+  }
+  ENC_HIP(hipStreamSynchronize(st));
+  g_enc_last[0] = a.n - nlong;
+  g_enc_last[1] = nlong;
+  g_enc_last[2] = a.nwaves;
+  g_enc_last[3] = total;
+  return TKV_OK;
+}
+
+}  // namespace
+
+int wal_encode_device_impl(const std::uint8_t* d_keys, const std::uint64_t* d_key_off, const std::uint32_t* d_key_len,
+                           const std::uint8_t* d_vals, const std::uint64_t* d_val_off, const std::uint32_t* d_val_len,
+                           const std::uint8_t* d_op, const std::uint8_t* d_tomb, const std::uint64_t* d_seq,
+                           std::uint64_t first_seq, std::uint64_t n, std::uint8_t* d_img, std::uint64_t cap,
+                           std::uint64_t* d_rec_off, std::uint32_t* d_crc, std::uint64_t* img_size, hipStream_t st) {
+  for (auto& v : g_enc_last) v = 0;
+  const DeviceTables* tabs = device_tables(kAlgoCrc32);
+  if (!tabs) return TKV_IO_ERROR;
+  EncScratch* sp = nullptr;
+  if (int rc = scratch(&sp)) return rc;
+  EncArgs a{};
+  a.keys = d_keys;
+  a.key_off = d_key_off;
+  a.key_len = d_key_len;
+  a.vals = d_vals;
+  a.val_off = d_val_off;
+  a.val_len = d_val_len;
+  a.op = d_op;
+  a.tomb = d_tomb;
+  a.seq = d_seq;
+  a.first_seq = first_seq;
+  a.n = n;
+  a.img = d_img;
+  a.rec_off = d_rec_off;
+  a.crc = d_crc;
+  a.fused = g_enc_fused.load() ? 1u : 0u;
+  a.tabs = tabs;
+  std::lock_guard<std::mutex> lk(sp->mu);
+  return encode_locked(*sp, a, cap, img_size, st);
+}
+
+}  // namespace tkv
+
+extern "C" {
+
+void tkv_debug_wal_encode_geometry(uint64_t out[4]) {
+  out[0] = tkv::kEncTile;
+  out[1] = tkv::kScanBlock;
+  out[2] = tkv::kLaneFold;
+  out[3] = tkv::kScanLevels;
+}
+
+void tkv_debug_wal_encode_last(uint64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = tkv::g_enc_last[i];
+}
+
+int tkv_debug_set_wal_encode_fused(int enable) { return tkv::g_enc_fused.exchange(enable ? 1 : 0); }
+
+}  // extern "C"

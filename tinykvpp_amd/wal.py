@@ -11,7 +11,9 @@ Here a whole slurped WAL (wal_reader::open, wal.cpp:204-240) is verified on the 
 copied to the device once, the record_len chain is walked there (speculative parallel walk with exact
 stitching) and every record's CRC is checked in ONE batch (tkv_wal_verify; tkv_wal_verify_device for
 an image already in HBM). Many records are stamped in one batch (tkv_wal_stamp) — the recovery loop
-of engine::create (engine.cpp:31-53) and group commit.
+of engine::create (engine.cpp:31-53) and group commit. A whole put batch held as keys, values and
+sequence numbers is encoded in one call (tkv_wal_encode: encode_batch; tkv_wal_encode_device for arenas
+already in HBM: encode_device), layout and CRCs included.
 """
 import ctypes
 import struct
@@ -47,6 +49,107 @@ def stamp(records):
 def encode(op, seq, key, value, tombstone):
     """wal_entry::encode: one stamped record (uses the batch path with n = 1)."""
     return stamp([encode_unstamped(op, seq, key, value, tombstone)])[0]
+
+
+def _arena(chunks):
+    """(arena uint8 array, offsets uint64, lengths uint32) of a list of bytes laid back to back."""
+    lens = np.array([len(c) for c in chunks], np.uint32)
+    offs = np.zeros(len(chunks), np.uint64)
+    if len(chunks) > 1:
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    arena = np.frombuffer(b"".join(chunks) + b"\0", np.uint8).copy()  # never empty: the pointer is required
+    return arena, offs, lens
+
+
+def encode_batch(keys, values, seqs=None, first_seq=0, ops=None, tombstones=None):
+    """wal_entry::encode for a whole batch (tkv_wal_encode): ``keys`` and ``values`` are lists of bytes,
+    ``seqs`` (default first_seq + i), ``ops`` (default PUT) and ``tombstones`` (default 0) per-record
+    sequences. The records are laid out on the host and stamped in one GPU batch. Returns
+    (image bytes, offsets): the records back to back and a uint64 numpy array of their start offsets."""
+    n = len(keys)
+    if len(values) != n:
+        raise ValueError("keys and values differ in length")
+    if n == 0:
+        return b"", np.zeros(0, np.uint64)
+    karena, koff, klen = _arena(keys)
+    varena, voff, vlen = _arena(values)
+    seq = None if seqs is None else np.ascontiguousarray(np.asarray(seqs, dtype=np.uint64))
+    op = None if ops is None else np.ascontiguousarray(np.asarray(ops, dtype=np.uint8))
+    tomb = None if tombstones is None else np.ascontiguousarray(np.asarray(tombstones).astype(bool).astype(np.uint8))
+    for name, a in (("seqs", seq), ("ops", op), ("tombstones", tomb)):
+        if a is not None and a.size != n:
+            raise ValueError(f"{name} must have one entry per record")
+    total = int(klen.sum(dtype=np.uint64) + vlen.sum(dtype=np.uint64)) + kMetadataSize * n
+    img = np.empty(total, np.uint8)
+    offs = np.empty(n, np.uint64)
+    size = ctypes.c_uint64(0)
+
+    def ptr(a):
+        return None if a is None else ctypes.c_void_p(a.ctypes.data)
+    check(load_library().tkv_wal_encode(ptr(karena), ptr(koff), ptr(klen), ptr(varena), ptr(voff), ptr(vlen),
+                                        ptr(op), ptr(tomb), ptr(seq), int(first_seq), n, ptr(img), total,
+                                        ptr(offs), None, ctypes.byref(size)))
+    return img[:size.value].tobytes(), offs
+
+
+def encode_device(keys, key_off, key_len, vals=None, val_off=None, val_len=None, op=None, tomb=None, seq=None,
+                  first_seq=0, out=None, stream=None):
+    """wal_entry::encode for a batch held on the device (tkv_wal_encode_device): ``keys`` / ``vals`` uint8
+    CUDA arenas, ``key_off`` / ``val_off`` int64 and ``key_len`` / ``val_len`` int32 (u32 values) CUDA
+    tensors with one entry per record, ``op`` / ``tomb`` uint8 and ``seq`` int64 per record (defaults:
+    no values, PUT, 0, first_seq + i). Returns (image, rec_off, crc): image is ``out[:total]`` (a uint8 CUDA
+    tensor of any alignment, e.g. the tail of an image the caller holds; allocated when not given),
+    rec_off an int64 tensor of the records' start offsets, crc an int32 tensor of their stamped CRCs.
+    An ``out`` that is too small raises with the size needed. Synchronous on ``stream``."""
+    import torch
+    from ._lib import BUFFER_OVERFLOW
+    from .crc32 import _check_data, _check_vec, _launch_stream
+    if keys.dtype != torch.uint8:
+        raise ValueError("keys must be a uint8 tensor")
+    _check_data(keys)
+    dev = keys.device
+    n = key_len.numel()
+    _check_vec("key_off", key_off, torch.int64, n, dev)
+    _check_vec("key_len", key_len, torch.int32, n, dev)
+    if val_len is not None:
+        if vals is None or val_off is None:
+            raise ValueError("val_len needs vals and val_off")
+        _check_vec("vals", vals, torch.uint8, 0, dev)
+        _check_vec("val_off", val_off, torch.int64, n, dev)
+        _check_vec("val_len", val_len, torch.int32, n, dev)
+    for name, t, dt in (("op", op, torch.uint8), ("tomb", tomb, torch.uint8), ("seq", seq, torch.int64)):
+        if t is not None:
+            _check_vec(name, t, dt, n, dev)
+    other = stream is not None and stream != torch.cuda.current_stream(dev)
+
+    def alloc(count, dtype):
+        t = torch.empty(count, dtype=dtype, device=dev)
+        if other:
+            t.record_stream(stream)
+        return t
+
+    def ptr(t):
+        return None if t is None else ctypes.c_void_p(t.data_ptr())
+    lib = load_library()
+    st = _launch_stream(stream, dev)
+    size = ctypes.c_uint64(0)
+
+    def call(img, cap, rec_off, crc):
+        return lib.tkv_wal_encode_device(ptr(keys), ptr(key_off), ptr(key_len), ptr(vals) if val_len is not None else None,
+                                         ptr(val_off) if val_len is not None else None, ptr(val_len), ptr(op), ptr(tomb),
+                                         ptr(seq), int(first_seq), n, img, cap, rec_off, crc, ctypes.byref(size), st)
+    if out is None:
+        rc = call(None, 0, None, None)  # the sizing call
+        if rc not in (OK, BUFFER_OVERFLOW):
+            check(rc)
+        out = alloc(size.value, torch.uint8)
+    _check_vec("out", out, torch.uint8, 0, dev)
+    rec_off, crc = alloc(n, torch.int64), alloc(n, torch.int32)
+    rc = call(ptr(out) if out.numel() else None, out.numel(), ptr(rec_off) if n else None, ptr(crc) if n else None)
+    if rc == BUFFER_OVERFLOW:
+        raise ValueError(f"out holds {out.numel()} bytes, the image needs {size.value}")
+    check(rc)
+    return out[:size.value], rec_off, crc
 
 
 def verify(wal_bytes):
