@@ -196,7 +196,12 @@ def test_round_trip_through_the_read_side(gpu, lib, oracle):
         image, rec_off, crc = tk.wal.encode_device(db.t["keys"], db.t["key_off"], db.t["key_len"], db.t["vals"],
                                                    db.t["val_off"], db.t["val_len"], db.t["op"], db.t["tomb"], db.t["seq"])
         total = image.numel()
-        assert total < 20 << 20 and total == int(expected(b)[0].size)
+        want, want_off, want_crc = expected(b, oracle)
+        assert total < 20 << 20 and total == int(want.size)
+        bad = np.flatnonzero(image.cpu().numpy() != want)
+        assert bad.size == 0, f"image differs at {bad[:8]} (first record {np.searchsorted(want_off, bad[0], 'right') - 1})"
+        assert np.array_equal(rec_off.cpu().numpy().view(np.uint64), want_off)
+        assert np.array_equal(crc.cpu().numpy().view(np.uint32), want_crc)
         assert tk.wal.verify_device(image) == ("ok", n, total)
         status, offs, stop, mseq = tk.wal.index_device(image, offsets32=True)
         assert (status, stop, mseq) == ("ok", total, int(b["seq"].max()))
@@ -224,7 +229,18 @@ def test_side_stream(gpu, lib, small_case):
                              db.t["val_len"], out=small)
 
 
-def test_python_host_path(gpu, lib):
+def list_batch(keys, vals, ops=None, tombs=None, seqs=None, first_seq=0):
+    """Lists of bytes as a batch of arrays (the arenas back to back), for expected()."""
+    klen, vlen = np.array([len(k) for k in keys], np.uint32), np.array([len(v) for v in vals], np.uint32)
+    arr = lambda x, dt: None if x is None else np.array(x, dt)  # noqa: E731
+    return dict(n=len(keys), keys=np.frombuffer(b"".join(keys) + b"\0", np.uint8),
+                key_off=(np.cumsum(klen, dtype=np.uint64) - klen), key_len=klen,
+                vals=np.frombuffer(b"".join(vals) + b"\0", np.uint8),
+                val_off=(np.cumsum(vlen, dtype=np.uint64) - vlen), val_len=vlen,
+                op=arr(ops, np.uint8), tomb=arr(tombs, np.uint8), seq=arr(seqs, np.uint64), first_seq=first_seq)
+
+
+def test_python_host_path(gpu, lib, oracle):
     recs = golden("wal.json")["records"]
     raw = [bytes.fromhex(r["hex"]) for r in recs]
     keys = [x[26:26 + int.from_bytes(x[18:22], "little")] for x in raw]
@@ -241,6 +257,12 @@ def test_python_host_path(gpu, lib):
     seqs = rng.integers(0, 1 << 62, n).tolist()
     want = b"".join(tk.wal.stamp([tk.wal.encode_unstamped(o, s, k, v, t)
                                   for o, s, k, v, t in zip(ops, seqs, keys, vals, tombs)]))
-    assert tk.wal.encode_batch(keys, vals, seqs=seqs, ops=ops, tombstones=tombs)[0] == want
+    image, offs = tk.wal.encode_batch(keys, vals, seqs=seqs, ops=ops, tombstones=tombs)
+    assert image == want
+    exp, exp_off, _ = expected(list_batch(keys, vals, ops, tombs, seqs), oracle)
+    assert image == exp.tobytes() and np.array_equal(offs, exp_off)
     want = b"".join(tk.wal.stamp([tk.wal.encode_unstamped(0, 77 + i, k, v, 0) for i, (k, v) in enumerate(zip(keys, vals))]))
-    assert tk.wal.encode_batch(keys, vals, first_seq=77)[0] == want
+    image, offs = tk.wal.encode_batch(keys, vals, first_seq=77)
+    assert image == want
+    exp, exp_off, _ = expected(list_batch(keys, vals, first_seq=77), oracle)
+    assert image == exp.tobytes() and np.array_equal(offs, exp_off)
