@@ -381,6 +381,42 @@ def test_long_payloads_at_region_ends(gpu, oracle):
             img[o] ^= 0x10
 
 
+def test_shared_scratch_grows_and_is_reused(gpu, oracle):
+    """verify_device, index_device and encode_device keep per-device scratch between calls, grown by
+    doubling through one shared piece of code. In one process on one device: a one-region image of a
+    few records, then about 4 MiB of 26-90-byte records (more than two 256-region scan blocks of the
+    index and 1024-record blocks of the encoder's size scan, every scratch array grown), then the first
+    image again in the grown scratch. The verify and the index must equal the sequential decode of the
+    image, the encode must equal the image wal_entry::encode lays out (wal_encode_util.expected)."""
+    from test_gpu_wal_index import decode
+    from wal_encode_util import DeviceBatch, expected, make_batch
+
+    rng = np.random.default_rng(2026)
+
+    def case(n):
+        body = rng.integers(0, 65, n)
+        klen = (rng.random(n) * (body + 1)).astype(np.int64)
+        b = make_batch(rng, klen, body - klen)
+        b["op"] = rng.integers(0, 2, n, dtype=np.uint8)
+        img, offs, crc = expected(b, oracle)
+        want, starts, mseq = decode(oracle, img, img.size)
+        assert want == ("ok", n, img.size) and np.array_equal(starts, offs)
+        return DeviceBatch(b, "cuda").t, torch.from_numpy(img).cuda(), img, offs, crc, want, mseq
+
+    small, large = case(5), case(72_500)
+    assert small[2].size <= REGION and large[2].size > (2 * 256 + 1) * REGION
+    for t, d, img, offs, crc, want, mseq in (small, large, small):
+        assert tk.wal.verify_device(d) == want
+        status, got, stop, seq = tk.wal.index_device(d)
+        assert (status, got.numel(), stop, seq) == want + (mseq,)
+        assert np.array_equal(got.cpu().numpy().view(np.uint64), offs)
+        out, rec_off, c = tk.wal.encode_device(t["keys"], t["key_off"], t["key_len"], t["vals"], t["val_off"],
+                                               t["val_len"], t["op"], t["tomb"], t["seq"])
+        assert np.array_equal(out.cpu().numpy(), img)
+        assert np.array_equal(rec_off.cpu().numpy().view(np.uint64), offs)
+        assert np.array_equal(c.cpu().numpy().view(np.uint32), crc)
+
+
 def test_image_over_4_gib(gpu, oracle):
     """An image past 4 GiB (kPos32Max) takes the sweep's 64-bit positions (wal_sweep<*, uint64_t>):
     257 records of exactly 16 MiB (zero values: passed over and checked by the long-payload batch at

@@ -171,22 +171,60 @@ __device__ __forceinline__ std::uint32_t mask_front(std::uint32_t d, std::uint32
   return d & static_cast<std::uint32_t>(0xFFFFFFFFull << (x < 32u ? x : 32u));
 }
 
-// Exclusive prefix sum over the 64 lanes (all active), and its total: an inclusive scan by DPP row
-// shifts within rows of 16, then the row totals broadcast into the rows above (row_bcast:15 / :31).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ std::uint32_t dpp_add(std::uint32_t x) {
-  return x + static_cast<std::uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, ROW_MASK, 0xF, false));
+__device__ __forceinline__ std::uint64_t readlane64(std::uint64_t v, std::uint32_t l) {
+  const std::uint32_t lo = __builtin_amdgcn_readlane(static_cast<std::uint32_t>(v), l);
+  const std::uint32_t hi = __builtin_amdgcn_readlane(static_cast<std::uint32_t>(v >> 32), l);
+  return (static_cast<std::uint64_t>(hi) << 32) | lo;
 }
-__device__ __forceinline__ std::uint32_t lane_prefix(std::uint32_t v, std::uint32_t* total) {
-  std::uint32_t x = v;
+
+// Exclusive prefix sum of u32 or u64 values over the 64 lanes (all active), and its total: an
+// inclusive scan by DPP row shifts within rows of 16, then the row totals broadcast into the rows above
+// (row_bcast:15 / :31). A u64 moves as its two halves.
+template <int CTRL, int ROW_MASK, typename T>
+__device__ __forceinline__ T dpp_add(T x) {
+  static_assert(std::is_same<T, std::uint32_t>::value || std::is_same<T, std::uint64_t>::value, "u32 or u64");
+  const std::uint32_t lo = static_cast<std::uint32_t>(
+      __builtin_amdgcn_update_dpp(0, static_cast<int>(static_cast<std::uint32_t>(x)), CTRL, ROW_MASK, 0xF, false));
+  if constexpr (sizeof(T) == 8) {
+    const std::uint32_t hi = static_cast<std::uint32_t>(
+        __builtin_amdgcn_update_dpp(0, static_cast<int>(static_cast<std::uint32_t>(x >> 32)), CTRL, ROW_MASK, 0xF, false));
+    return x + ((static_cast<std::uint64_t>(hi) << 32) | lo);
+  } else {
+    return x + lo;
+  }
+}
+template <typename T>
+__device__ __forceinline__ T lane_prefix(T v, T* total) {
+  T x = v;
   x = dpp_add<0x111, 0xF>(x);  // row_shr:1
   x = dpp_add<0x112, 0xF>(x);  // row_shr:2
   x = dpp_add<0x114, 0xF>(x);  // row_shr:4
   x = dpp_add<0x118, 0xF>(x);  // row_shr:8
   x = dpp_add<0x142, 0xA>(x);  // row_bcast:15 into rows 1 and 3
   x = dpp_add<0x143, 0xC>(x);  // row_bcast:31 into rows 2 and 3
-  *total = static_cast<std::uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), 63));
+  if constexpr (sizeof(T) == 8) *total = readlane64(x, 63);
+  else *total = static_cast<std::uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), 63));
   return x - v;
+}
+
+// The same over a workgroup of THREADS threads (every one active), and the workgroup's total: the
+// wave scans, then the wave totals through LDS. One barrier; a kernel calls it once.
+template <typename T, unsigned THREADS>
+__device__ __forceinline__ T block_prefix(T v, T* total) {
+  __shared__ T wsum[THREADS / 64];
+  T wt;
+  const T pre = lane_prefix(v, &wt);
+  const std::uint32_t wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 0) wsum[wv] = wt;
+  __syncthreads();
+  T before = 0, all = 0;
+#pragma unroll
+  for (std::uint32_t k = 0; k < THREADS / 64; ++k) {
+    before += k < wv ? wsum[k] : 0u;
+    all += wsum[k];
+  }
+  *total = all;
+  return before + pre;
 }
 
 // Minimum of v over the 64 lanes, wave-uniform (as wave_max; lanes past a row's edge read ~0).
@@ -653,12 +691,6 @@ __device__ __forceinline__ std::uint32_t wave_prefix_xor(std::uint32_t v) {
   v ^= __builtin_amdgcn_update_dpp(0u, v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
   v ^= __builtin_amdgcn_update_dpp(0u, v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
   return v;
-}
-
-__device__ __forceinline__ std::uint64_t readlane64(std::uint64_t v, std::uint32_t l) {
-  const std::uint32_t lo = __builtin_amdgcn_readlane(static_cast<std::uint32_t>(v), l);
-  const std::uint32_t hi = __builtin_amdgcn_readlane(static_cast<std::uint32_t>(v >> 32), l);
-  return (static_cast<std::uint64_t>(hi) << 32) | lo;
 }
 
 // Stream-mode row partition: wave w (of W, 16 to a workgroup) walks rows [stream_row0(w), stream_row0(w+1))

@@ -1229,6 +1229,11 @@ const DeviceTables* device_tables(int algo) {
   return c->d_tabs[algo];
 }
 
+int device_cu_count() {
+  DevCtx* c = nullptr;
+  return get_ctx(&c) ? 0 : c->ncu;
+}
+
 }  // namespace tkv
 
 using namespace tkv;

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tkv_crc32_device.h"
+#include "tkv_device_util.h"
 
 namespace tkv {
 
@@ -1473,20 +1474,16 @@ hipError_t launch_packed_small_gen(const RowsArgs& a, unsigned grid, hipStream_t
 // Uniform lane-block batch (a.len <= kLaneMax): ALIGN from the base pointer and the stride.
 template <int ALIGN, int NG>
 void launch_lanes_shape(RowsArgs a, unsigned ncu, hipStream_t st) {
-  const std::uint64_t steps = (static_cast<std::uint64_t>(a.nblocks) + 63u) / 64u;
-  const std::uint64_t waves = kThreads / 64u;
-  const std::uint64_t grid = std::max<std::uint64_t>(1, std::min<std::uint64_t>(ncu, (steps + waves - 1) / waves));
-  a.nwaves = static_cast<std::uint32_t>(grid * waves);
-  hipLaunchKernelGGL((crc_lanes_n<ALIGN, NG>), dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, st, a);
+  const unsigned grid = wave_grid(a.nblocks, ncu, kThreads / 64u);
+  a.nwaves = grid * (kThreads / 64u);
+  hipLaunchKernelGGL((crc_lanes_n<ALIGN, NG>), dim3(grid), dim3(kThreads), 0, st, a);
 }
 
 template <int ALIGN, int NF>
 void launch_lanes_r_nf(RowsArgs a, unsigned ncu, hipStream_t st) {
-  const std::uint64_t steps = (static_cast<std::uint64_t>(a.nblocks) + 63u) / 64u;
-  const std::uint64_t waves = kThreads / 64u;
-  const std::uint64_t grid = std::max<std::uint64_t>(1, std::min<std::uint64_t>(ncu, (steps + waves - 1) / waves));
-  a.nwaves = static_cast<std::uint32_t>(grid * waves);
-  hipLaunchKernelGGL((crc_lanes_r<ALIGN, NF>), dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, st, a);
+  const unsigned grid = wave_grid(a.nblocks, ncu, kThreads / 64u);
+  a.nwaves = grid * (kThreads / 64u);
+  hipLaunchKernelGGL((crc_lanes_r<ALIGN, NF>), dim3(grid), dim3(kThreads), 0, st, a);
 }
 template <int ALIGN, int NF = 1>
 void launch_lanes_r(const RowsArgs& a, std::uint32_t nf, unsigned ncu, hipStream_t st) {
@@ -1520,12 +1517,10 @@ hipError_t launch_lanes(const RowsArgs& a, unsigned ncu, hipStream_t st) {
   // under 28 bytes (a step copies more than it folds) measured slower and keep crc_lanes_n.
   if (a.init_raw == nullptr && align != 16 && a.len >= 28u && a.stride <= dev::kLanesLdsMaxStride &&
       15u + 63u * a.stride + a.len + 8u <= dev::kLanesLdsBuf) {
-    const std::uint64_t steps = (static_cast<std::uint64_t>(a.nblocks) + 63u) / 64u;
-    const std::uint64_t waves = kThreads / 64u;
-    const std::uint64_t grid = std::max<std::uint64_t>(1, std::min<std::uint64_t>(ncu, (steps + waves - 1) / waves));
+    const unsigned grid = wave_grid(a.nblocks, ncu, kThreads / 64u);
     RowsArgs b = a;
-    b.nwaves = static_cast<std::uint32_t>(grid * waves);
-    const dim3 g(static_cast<unsigned>(grid)), t(kThreads);
+    b.nwaves = grid * (kThreads / 64u);
+    const dim3 g(grid), t(kThreads);
     const std::uint32_t nw = (a.len + 3u) / 4u;  // words to read (the tail's included)
     const std::uint32_t kb = (15u + 63u * a.stride + a.len + 8u + 1023u) / 1024u;  // KiB a step copies
 #define TKV_LANES_LDS_KB(RA, NW)                                                             \
@@ -1570,18 +1565,14 @@ hipError_t launch_fixup(const RowsArgs& a, hipStream_t st) {
 // Waves of crc_list_lanes for a batch of nblocks: one workgroup per CU (at most kListMaxGroups) or
 // fewer when the 64-block steps run out (tkv_debug_list_lanes_waves reports it to the tests).
 std::uint32_t list_lanes_waves(std::uint64_t nblocks, unsigned ncu) {
-  const std::uint64_t steps = (nblocks + 63u) / 64u;
-  const std::uint64_t grid = std::max<std::uint64_t>(
-      1, std::min<std::uint64_t>(std::min<std::uint64_t>(ncu, kListMaxGroups), (steps + kListWaves - 1) / kListWaves));
-  return static_cast<std::uint32_t>(grid * kListWaves);
+  return wave_grid(nblocks, ncu, kListWaves, kListMaxGroups) * kListWaves;
 }
 
 // One-pass lane kernel of an irregular batch (default initial register): see crc_list_lanes.
 hipError_t launch_list_lanes(const RowsArgs& a, unsigned ncu, hipStream_t st) {
   RowsArgs b = a;
   b.nwaves = list_lanes_waves(a.nblocks, ncu);
-  const std::uint64_t grid = b.nwaves / kListWaves;
-  hipLaunchKernelGGL(crc_list_lanes, dim3(static_cast<unsigned>(grid)), dim3(kListThreads), 0, st, b);
+  hipLaunchKernelGGL(crc_list_lanes, dim3(b.nwaves / kListWaves), dim3(kListThreads), 0, st, b);
   return hipGetLastError();
 }
 

@@ -31,6 +31,8 @@ int batch_host_multi_impl(int algo, const int* devices, int ndev, const std::uin
 int set_error(int code, const char* msg);
 // Constant tables of `algo` on the current device (creates the device context); nullptr on error.
 const DeviceTables* device_tables(int algo);
+// Compute units of the current device (from its device context, created if need be); 0 on error.
+int device_cu_count();
 
 // tkv_crc32_kernels.hip: SSTable stamp fix-up (see tkv_sst_block_crcs_device).
 hipError_t launch_sst_fix(std::uint8_t* file, const std::uint64_t* offsets, const std::uint32_t* sizes,

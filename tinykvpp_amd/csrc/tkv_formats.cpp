@@ -15,6 +15,7 @@
 #include "tkv_crc32.h"
 #include "tkv_engine.h"
 #include "tkv_wal_device.h"
+#include "tkv_wal_layout.h"
 
 using namespace tkv;
 
@@ -53,8 +54,6 @@ std::uint32_t field_term(std::uint32_t v, std::uint64_t z) {
 }
 
 // ---- WAL record_len chain (wal.cpp:63-87) ----------------------------------------------------------
-constexpr std::uint64_t kWalMeta = 26;  // wal.hpp:21-27 kMetadataSize
-
 struct Chain {
   std::vector<std::uint64_t> pos;  // record starts, in order
   std::vector<std::uint32_t> len;  // their record_len (payload bytes after the 8-byte prefix)
@@ -83,18 +82,18 @@ void walk(const std::uint8_t* w, std::uint64_t size, std::uint64_t start, std::u
     }
     std::uint32_t rlen, crc, klen, vlen;
     std::memcpy(&rlen, w + p, 4);
-    if (static_cast<std::uint64_t>(rlen) + 8 > size - p) {
+    if (static_cast<std::uint64_t>(rlen) + kWalPayload > size - p) {
       c.err = true;
       break;
     }
-    std::memcpy(&crc, w + p + 4, 4);  // the header's other fields share its cache line
-    std::memcpy(&klen, w + p + 18, 4);
-    std::memcpy(&vlen, w + p + 22, 4);
+    std::memcpy(&crc, w + p + kWalCrc, 4);  // the header's other fields share its cache line
+    std::memcpy(&klen, w + p + kWalKeyLen, 4);
+    std::memcpy(&vlen, w + p + kWalValLen, 4);
     c.pos.push_back(p);
     c.len.push_back(rlen);
     c.crc.push_back(crc);
-    c.kv_ok.push_back(kWalMeta + static_cast<std::uint64_t>(klen) + vlen <= 8 + static_cast<std::uint64_t>(rlen));
-    p += 8 + static_cast<std::uint64_t>(rlen);
+    c.kv_ok.push_back(kWalMeta + static_cast<std::uint64_t>(klen) + vlen <= kWalPayload + static_cast<std::uint64_t>(rlen));
+    p += kWalPayload + static_cast<std::uint64_t>(rlen);
   }
   c.end = p;
 }
@@ -134,10 +133,10 @@ bool plausible(const std::uint8_t* w, std::uint64_t size, std::uint64_t p) {
   if (size - p < kWalMeta) return false;
   std::uint32_t rlen, klen, vlen;
   std::memcpy(&rlen, w + p, 4);
-  std::memcpy(&klen, w + p + 18, 4);
-  std::memcpy(&vlen, w + p + 22, 4);
-  return w[p + 8] <= 1 && w[p + 17] <= 1 && static_cast<std::uint64_t>(rlen) == 18ull + klen + vlen &&
-         static_cast<std::uint64_t>(rlen) + 8 <= size - p;
+  std::memcpy(&klen, w + p + kWalKeyLen, 4);
+  std::memcpy(&vlen, w + p + kWalValLen, 4);
+  return w[p + kWalOp] <= 1 && w[p + kWalTomb] <= 1 && static_cast<std::uint64_t>(rlen) == 18ull + klen + vlen &&
+         static_cast<std::uint64_t>(rlen) + kWalPayload <= size - p;
 }
 
 // The chain of the whole image, identical to a sequential walk from 0. Each record start depends on
@@ -206,7 +205,7 @@ std::uint64_t max_sequence_of(const std::uint8_t* w, const std::vector<std::uint
   std::uint64_t mx = 0;
   for (const std::uint64_t p : pos) {
     std::uint64_t seq;
-    std::memcpy(&seq, w + p + 9, 8);
+    std::memcpy(&seq, w + p + kWalSeq, 8);
     mx = std::max(mx, seq);
   }
   return mx;
@@ -333,7 +332,7 @@ int wal_verify_host_walk(const uint8_t* h_wal, uint64_t size, uint64_t* n_good, 
     const std::size_t nrec = ch.pos.size();
     off[j].resize(nrec);
     got[j].resize(nrec);
-    for (std::size_t i = 0; i < nrec; ++i) off[j][i] = ch.pos[i] + 8;
+    for (std::size_t i = 0; i < nrec; ++i) off[j][i] = ch.pos[i] + kWalPayload;
     if (nrec)
       crc_th.emplace_back([&, j, nrec] {
         if (hipSetDevice(dev) != hipSuccess) {
@@ -373,12 +372,12 @@ int tkv_wal_stamp(uint8_t* h_buf, const uint64_t* h_offsets, const uint32_t* h_s
   std::vector<std::uint64_t> off(n);
   std::vector<std::uint32_t> len(n), crc(n);
   for (std::uint64_t i = 0; i < n; ++i) {
-    if (h_sizes[i] < 8) return set_error(TKV_INVALID_ARGUMENT, "WAL record shorter than its 8-byte prefix");
-    off[i] = h_offsets[i] + 8;  // wal.cpp:54-57: CRC over [8, size)
-    len[i] = h_sizes[i] - 8;
+    if (h_sizes[i] < kWalPayload) return set_error(TKV_INVALID_ARGUMENT, "WAL record shorter than its 8-byte prefix");
+    off[i] = h_offsets[i] + kWalPayload;  // wal.cpp:54-57: CRC over [8, size)
+    len[i] = h_sizes[i] - kWalPayload;
   }
   if (int rc = batch_host_impl(kAlgoCrc32, h_buf, off.data(), len.data(), nullptr, crc.data(), n)) return rc;
-  parallel_for(n, [&](std::uint64_t i) { std::memcpy(h_buf + h_offsets[i] + 4, &crc[i], 4); });  // wal.cpp:58
+  parallel_for(n, [&](std::uint64_t i) { std::memcpy(h_buf + h_offsets[i] + kWalCrc, &crc[i], 4); });  // wal.cpp:58
   return TKV_OK;
 }
 
@@ -418,7 +417,7 @@ int encode_offsets(const EncodeIn& in, std::vector<std::uint64_t>& off) {
     const std::uint64_t rl = 18ull + in.key_len[i] + (in.val_len ? in.val_len[i] : 0u);
     if (rl > 0xFFFFFFFFull) return set_error(TKV_INVALID_ARGUMENT, "WAL encode: 18 + key_len + val_len does not fit u32");
     off[i] = run;
-    run += rl + 8;
+    run += rl + kWalPayload;
   }
   off[in.n] = run;
   return TKV_OK;
@@ -432,12 +431,12 @@ void encode_layout(const EncodeIn& in, const std::vector<std::uint64_t>& off, st
     const std::uint32_t rl = 18u + kl + vl, zero = 0;
     const std::uint64_t seq = in.seq ? in.seq[i] : in.first_seq + i;
     std::memcpy(r, &rl, 4);
-    std::memcpy(r + 4, &zero, 4);
-    r[8] = in.op ? in.op[i] : 0;
-    for (int b = 0; b < 8; ++b) r[9 + b] = static_cast<std::uint8_t>(seq >> (8 * b));
-    r[17] = in.tomb && in.tomb[i] ? 1 : 0;
-    for (int b = 0; b < 4; ++b) r[18 + b] = static_cast<std::uint8_t>(kl >> (8 * b));
-    for (int b = 0; b < 4; ++b) r[22 + b] = static_cast<std::uint8_t>(vl >> (8 * b));
+    std::memcpy(r + kWalCrc, &zero, 4);
+    r[kWalOp] = in.op ? in.op[i] : 0;
+    for (int b = 0; b < 8; ++b) r[kWalSeq + b] = static_cast<std::uint8_t>(seq >> (8 * b));
+    r[kWalTomb] = in.tomb && in.tomb[i] ? 1 : 0;
+    for (int b = 0; b < 4; ++b) r[kWalKeyLen + b] = static_cast<std::uint8_t>(kl >> (8 * b));
+    for (int b = 0; b < 4; ++b) r[kWalValLen + b] = static_cast<std::uint8_t>(vl >> (8 * b));
     if (kl) std::memcpy(r + kWalMeta, in.keys + in.key_off[i], kl);
     if (vl) std::memcpy(r + kWalMeta + kl, in.vals + in.val_off[i], vl);
   });
@@ -492,11 +491,11 @@ int tkv_wal_encode(const uint8_t* h_keys, const uint64_t* h_key_off, const uint3
   std::vector<std::uint64_t> poff(n);
   std::vector<std::uint32_t> len(n), crc(n);
   for (std::uint64_t i = 0; i < n; ++i) {
-    poff[i] = off[i] + 8;
-    len[i] = static_cast<std::uint32_t>(off[i + 1] - off[i] - 8);
+    poff[i] = off[i] + kWalPayload;
+    len[i] = static_cast<std::uint32_t>(off[i + 1] - off[i] - kWalPayload);
   }
   if (int rc = batch_host_impl(kAlgoCrc32, h_img, poff.data(), len.data(), nullptr, crc.data(), n)) return rc;
-  parallel_for(n, [&](std::uint64_t i) { std::memcpy(h_img + off[i] + 4, &crc[i], 4); });
+  parallel_for(n, [&](std::uint64_t i) { std::memcpy(h_img + off[i] + kWalCrc, &crc[i], 4); });
   if (ptr_ok(h_rec_off)) std::memcpy(h_rec_off, off.data(), n * sizeof(std::uint64_t));
   if (ptr_ok(h_crc)) std::memcpy(h_crc, crc.data(), n * sizeof(std::uint32_t));
   return TKV_OK;

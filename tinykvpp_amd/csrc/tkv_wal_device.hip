@@ -49,14 +49,15 @@
 
 #include "tkv_crc32.h"
 #include "tkv_crc32_device.h"
+#include "tkv_device_util.h"
 #include "tkv_engine.h"
 #include "tkv_wal_device.h"
 #include "tkv_wal_fold.h"
+#include "tkv_wal_layout.h"
 
 namespace tkv {
 namespace {
 
-constexpr std::uint64_t kWalMeta = 26;          // wal.hpp:21-27 kMetadataSize
 constexpr std::uint64_t kNone = ~0ull;
 constexpr std::uint32_t kRegion = 7168;  // image bytes per region (one wave step)
 constexpr int kRows = kRegion / 1024;           // 1 KiB load rows per region
@@ -175,7 +176,7 @@ template <typename P, int NG>
 __device__ __forceinline__ P search_piece(const std::uint8_t* win, P rs, std::uint32_t o, P ps, P qe, P size) {
   static_assert(NG % 2 == 0, "groups of 16 positions in pairs (64-bit masks)");
   if (ps >= qe) return kNoneP<P>;
-  const std::uint32_t b0 = static_cast<std::uint32_t>(ps - rs) + o + 8u;
+  const std::uint32_t b0 = static_cast<std::uint32_t>(ps - rs) + o + kWalOp;
   const std::uint32_t a16 = b0 & ~15u;
   const std::uint32_t sh = __builtin_amdgcn_readfirstlane(b0 & 15u);
   const uint4* g = reinterpret_cast<const uint4*>(win + a16);
@@ -224,10 +225,10 @@ __device__ __forceinline__ P search_piece(const std::uint8_t* win, P rs, std::ui
     const std::uint32_t j = static_cast<std::uint32_t>(__builtin_ctz((yv >> i) & 0x01010101u)) >> 3;
     const std::uint32_t pos = 16u * gi + 4u * i + j - sh;  // from ps
     if (pos >= span) return kNoneP<P>;  // (every later candidate lies further on)
-    const std::uint32_t b = b0 - 8u + pos;
-    const std::uint64_t rl = rd32(win, b), kl = rd32(win, b + 18u), vl = rd32(win, b + 22u);
+    const std::uint32_t b = b0 - kWalOp + pos;
+    const std::uint64_t rl = rd32(win, b), kl = rd32(win, b + kWalKeyLen), vl = rd32(win, b + kWalValLen);
     const P q = ps + pos;
-    if (rl == 18u + kl + vl && static_cast<P>(rl) <= size - q - 8u) return q;  // (size - q >= 26)
+    if (rl == 18u + kl + vl && static_cast<P>(rl) <= size - q - kWalPayload) return q;  // (size - q >= 26)
     const std::uint64_t bit = 1ull << ((hw ? 32u : 0u) + 8u * j + i);
 #pragma unroll
     for (int k = 0; k < NG / 2; ++k)
@@ -266,7 +267,7 @@ __device__ __forceinline__ void walk_piece(const std::uint8_t* win, P rs, std::u
       act = false;
     } else {
       const std::uint32_t rl = rd32(win, static_cast<std::uint32_t>(p - rs) + o);
-      if (static_cast<P>(rl) > size - p - 8u) {  // (size - p >= 26)
+      if (static_cast<P>(rl) > size - p - kWalPayload) {  // (size - p >= 26)
         wk.broke = true;
         act = false;
       } else {
@@ -310,8 +311,8 @@ template <typename P>
 __device__ __forceinline__ bool plausible_at(const std::uint8_t* win, P rs, std::uint32_t o, P r) {
   if (r == kNoneP<P>) return false;
   const std::uint32_t b = static_cast<std::uint32_t>(r - rs) + o;
-  const std::uint64_t rl = rd32(win, b), kl = rd32(win, b + 18u), vl = rd32(win, b + 22u);
-  return (rd32(win, b + 8u) & 0xFFu) <= 1u && (rd32(win, b + 17u) & 0xFFu) <= 1u && rl == 18u + kl + vl;
+  const std::uint64_t rl = rd32(win, b), kl = rd32(win, b + kWalKeyLen), vl = rd32(win, b + kWalValLen);
+  return (rd32(win, b + kWalOp) & 0xFFu) <= 1u && (rd32(win, b + kWalTomb) & 0xFFu) <= 1u && rl == 18u + kl + vl;
 }
 
 // Region r's granules: 1 KiB load rows k = 0..kRows-1, lane l's 16 bytes at row offset 16 l, as
@@ -509,12 +510,12 @@ __device__ __forceinline__ void sweep_wave(const SweepArgs& a, std::uint8_t* win
             const bool cj = carry_lane && kk == nl;  // this lane folds the carry
             const std::uint32_t so = act ? list[kk] : 0u;
             const std::uint32_t b = so + o;
-            const std::uint32_t rl = rd32(win, b), stored = rd32(win, b + 4u);
-            const std::uint32_t kl = rd32(win, b + 18u), vl = rd32(win, b + 22u);
-            const bool kv_ok = kWalMeta + static_cast<std::uint64_t>(kl) + vl <= 8ull + rl;  // wal.cpp:118-121
+            const std::uint32_t rl = rd32(win, b), stored = rd32(win, b + kWalCrc);
+            const std::uint32_t kl = rd32(win, b + kWalKeyLen), vl = rd32(win, b + kWalValLen);
+            const bool kv_ok = kWalMeta + static_cast<std::uint64_t>(kl) + vl <= std::uint64_t{kWalPayload} + rl;  // wal.cpp:118-121
             const bool lng = act && rl > kLaneFold;
             const std::uint32_t fn = cj ? eo - o : act && !lng ? rl : 0u;
-            const std::uint32_t raw = fold_raw(win, tab, kc, cj ? o : b + 8u, fn);
+            const std::uint32_t raw = fold_raw(win, tab, kc, cj ? o : b + kWalPayload, fn);
             const std::uint32_t crc = raw ^ inj[fn] ^ 0xFFFFFFFFu;
             if (carry_lane && base + 64u > nl)
               carry_v = static_cast<std::uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(raw), static_cast<int>(nl - base)));
@@ -529,7 +530,7 @@ __device__ __forceinline__ void sweep_wave(const SweepArgs& a, std::uint8_t* win
                                                                       __builtin_amdgcn_mbcnt_lo(static_cast<std::uint32_t>(mb), 0u));
               if (med) {
                 if (at < rcap) {
-                  const std::uint32_t rend = o + kRegion, pa = b + 8u, pz = b + 8u + rl;
+                  const std::uint32_t rend = o + kRegion, pa = b + kWalPayload, pz = pa + rl;
                   R[3 * at] = std::min(pa, rend) | std::min(pz, rend) << 16;
                   R[3 * at + 1] = kk | (pz <= rend ? kRangeWhole : kRangeHead) << 9 | b << 16;
                 } else {
@@ -554,7 +555,7 @@ __device__ __forceinline__ void sweep_wave(const SweepArgs& a, std::uint8_t* win
               const std::uint64_t idx = at + __builtin_amdgcn_mbcnt_hi(static_cast<std::uint32_t>(lb >> 32),
                                                                        __builtin_amdgcn_mbcnt_lo(static_cast<std::uint32_t>(lb), 0u));
               if (gnt && idx < a.l_cap) {
-                a.l_off[idx] = static_cast<std::uint64_t>(rs) + so + 8u;
+                a.l_off[idx] = static_cast<std::uint64_t>(rs) + so + kWalPayload;
                 a.l_len[idx] = rl;
                 a.l_crc[idx] = stored;
                 a.l_reg[idx] = rr;
@@ -578,7 +579,7 @@ __device__ __forceinline__ void sweep_wave(const SweepArgs& a, std::uint8_t* win
               acc = R[3 * lane + 2];
             }
             if (Er > rs && !carry_lane) carry_v = static_cast<std::uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(acc)));
-            const std::uint32_t st = lane < nr && kd != kRangeCarry ? rd32(win, bo + 4u) : 0u;
+            const std::uint32_t st = lane < nr && kd != kRangeCarry ? rd32(win, bo + kWalCrc) : 0u;
             const bool mbad = lane < nr && kd == kRangeWhole && (acc ^ 0xFFFFFFFFu) != st;
             const std::uint32_t mk = dev::wave_min(mbad ? kki : 0xFFFFFFFFu);
             bad_k = std::min(bad_k, mk);
@@ -608,7 +609,7 @@ __device__ __forceinline__ void sweep_wave(const SweepArgs& a, std::uint8_t* win
       // (no record walked) continues the hop that led there.
       bool ghop = false;
       if ((flags & kChain) && !(flags & kBroke) && Xout < size && Xout / kRegion > static_cast<P>(rr) + 1u) {
-        if (Lr != kNo) hop_giant = Xout - Lr - 8u > static_cast<P>(kMedMax);
+        if (Lr != kNo) hop_giant = Xout - Lr - kWalPayload > static_cast<P>(kMedMax);
         ghop = hop_giant;
       }
       if (ghop) flags |= kGiantHop;
@@ -786,7 +787,7 @@ __global__ void wal_long_gather(SweepArgs a, const std::uint64_t* l_base, std::u
   // list records of any length, hundreds of MB each. They go to the batch empty and marked stale.
   const std::uint64_t off = a.l_off[src];
   const std::uint32_t reg = a.l_reg[src], meta = a.l_meta[src];
-  const bool live = (meta >> 9) == (a.fl[reg] >> 8) && off - 8u < std::min<std::uint64_t>(res[kResP], res[kResQ]);
+  const bool live = (meta >> 9) == (a.fl[reg] >> 8) && off - kWalPayload < std::min<std::uint64_t>(res[kResP], res[kResQ]);
   d_off[j] = off;
   d_len[j] = live ? a.l_len[src] : 0u;
   d_crc[j] = a.l_crc[src];
@@ -842,7 +843,7 @@ __device__ bool crossing_bad(const SweepArgs& a, std::uint64_t r, std::uint64_t*
   if (!(f & kChain) || (f & kBroke)) return false;
   const DeviceTables* t = a.tabs;
   const std::uint32_t cp = a.cm_pos[r];
-  const std::uint64_t s = r * kRegion + (cp & 0xFFFFu), A = s + 8u, B = A + len;
+  const std::uint64_t s = r * kRegion + (cp & 0xFFFFu), A = s + kWalPayload, B = A + len;
   std::uint32_t reg = a.cm_part[r];
   for (std::uint64_t q = r + 1u; q < a.nreg; ++q) {
     const std::uint64_t rsq = q * kRegion, req = rsq + kRegion, y = std::min(B, req);
@@ -878,7 +879,7 @@ __device__ void fin_min_one(const SweepArgs& a, std::uint64_t i, const std::uint
   if (i < nlong) {
     const std::uint32_t r = a.l_reg[i];
     if ((a.l_meta[i] >> 9) == (a.fl[r] >> 8) && got[i] != a.l_crc[i])
-      atomicMin(&a.res[kResP], static_cast<unsigned long long>(a.l_off[i] - 8u));
+      atomicMin(&a.res[kResP], static_cast<unsigned long long>(a.l_off[i] - kWalPayload));
   }
 }
 
@@ -957,7 +958,7 @@ __global__ __launch_bounds__(512) void wal_finish(SweepArgs a, const std::uint32
   }
   if (bad && i < nlong) {
     const std::uint32_t r = a.l_reg[i];
-    if ((a.l_meta[i] >> 9) == (a.fl[r] >> 8) && got[i] != a.l_crc[i] && a.l_off[i] - 8u == P)
+    if ((a.l_meta[i] >> 9) == (a.fl[r] >> 8) && got[i] != a.l_crc[i] && a.l_off[i] - kWalPayload == P)
       atomicExch(&a.res[kResLidx], static_cast<unsigned long long>(a.l_meta[i] & 0x1FFu));
   }
   // block sum
@@ -1028,31 +1029,12 @@ __device__ __forceinline__ std::uint32_t region_good(const SweepArgs& a, std::ui
   return (a.fl[i] & kChain) && i <= rb ? a.cnt[i] : 0u;
 }
 
-// Exclusive prefix of v over the block's kScanThreads threads (DPP scan per wave, wave totals through
-// LDS) and the block's total.
-__device__ __forceinline__ std::uint32_t block_prefix(std::uint32_t v, std::uint32_t* total) {
-  __shared__ std::uint32_t wsum[kScanThreads / 64];
-  std::uint32_t wt;
-  const std::uint32_t pre = lane_prefix(v, &wt);
-  const std::uint32_t wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63u) == 0) wsum[wv] = wt;
-  __syncthreads();
-  std::uint32_t before = 0, all = 0;
-#pragma unroll
-  for (std::uint32_t k = 0; k < kScanThreads / 64; ++k) {
-    before += k < wv ? wsum[k] : 0u;
-    all += wsum[k];
-  }
-  *total = all;
-  return before + pre;
-}
-
 __global__ __launch_bounds__(kScanThreads) void wal_idx_count(SweepArgs a, IndexArgs x) {
   const std::uint64_t i = blockIdx.x * static_cast<std::uint64_t>(kScanThreads) + threadIdx.x;
   const std::uint32_t c = i < a.nreg ? region_good(a, i) : 0u;
   if (i < a.nreg) x.good[i] = c;
   std::uint32_t total;
-  (void)block_prefix(c, &total);
+  (void)dev::block_prefix<std::uint32_t, kScanThreads>(c, &total);
   if (threadIdx.x == 0) x.bsum[blockIdx.x] = total;
 }
 
@@ -1089,7 +1071,7 @@ __global__ __launch_bounds__(kScanThreads) void wal_idx_top(IndexArgs x) {
 __global__ __launch_bounds__(kScanThreads) void wal_idx_base(SweepArgs a, IndexArgs x) {
   const std::uint64_t i = blockIdx.x * static_cast<std::uint64_t>(kScanThreads) + threadIdx.x;
   std::uint32_t total;
-  const std::uint32_t pre = block_prefix(i < a.nreg ? x.good[i] : 0u, &total);
+  const std::uint32_t pre = dev::block_prefix<std::uint32_t, kScanThreads>(i < a.nreg ? x.good[i] : 0u, &total);
   if (i < a.nreg) x.base[i] = x.bsum[blockIdx.x] + pre;
 }
 
@@ -1186,7 +1168,7 @@ __global__ __launch_bounds__(64 * kIdxWaves) void wal_idx_emit(SweepArgs a, Inde
   for (std::uint32_t j = 0; j < kStore; ++j) {
     if (on && j < wk.n && pre + j < n) {
       const std::uint32_t b = wk.st[j] + o;
-      const std::uint64_t seq = rd32(win, b + 9u) | static_cast<std::uint64_t>(rd32(win, b + 13u)) << 32;
+      const std::uint64_t seq = rd32(win, b + kWalSeq) | static_cast<std::uint64_t>(rd32(win, b + kWalSeq + 4u)) << 32;
       mx = std::max(mx, seq);
       const std::uint64_t k = b0 + pre + j;
       if (k < x.cap) {
@@ -1247,7 +1229,6 @@ struct WalScratch {
   hipEvent_t slab_free[2] = {nullptr, nullptr};
   hipStream_t st = nullptr;   // copies of host images
   hipStream_t stc = nullptr;  // device work on host images
-  int ncu = 0;
   // record index: per region good (u32) and base (u64); per scan block sums (u64); result words; the
   // offsets of a host image's records
   std::uint64_t cap_idx = 0, cap_bsum = 0, cap_off = 0;
@@ -1290,34 +1271,12 @@ constexpr std::uint64_t kRoundBudget = 256;
 // the budget in force (tkv_debug_set_wal_round_budget: tests reach the host-walk hand-over with a small one)
 std::atomic<std::uint64_t> g_round_budget{kRoundBudget};
 
-std::mutex g_wal_mu;
-WalScratch* g_wal[64] = {};
-
 // What the calling thread's last WAL verify did (tkv_debug_wal_last).
 thread_local std::uint64_t g_last[4] = {0, 0, 0, 0};  // rounds, host walk needed, image copied, no fix-up
 // per fix-up round of the calling thread's last verify: failing boundaries, tasks, the longest task's
 // range and all tasks' ranges in regions, the most regions one task walked and all walked regions
 // (tkv_debug_wal_rounds)
 thread_local std::vector<std::uint64_t> g_rounds;
-
-#define WAL_HIP(call)                                                            \
-  do {                                                                           \
-    hipError_t e_ = (call);                                                      \
-    if (e_ != hipSuccess) return set_error(TKV_IO_ERROR, hipGetErrorString(e_)); \
-  } while (0)
-
-unsigned blocks(std::uint64_t n, unsigned t) { return static_cast<unsigned>((n + t - 1) / t); }
-
-int grow(void** p, std::uint64_t* cap, std::uint64_t want, std::uint64_t unit) {
-  if (want <= *cap) return TKV_OK;
-  const std::uint64_t c = std::max<std::uint64_t>(want, 2 * *cap);
-  WAL_HIP(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  WAL_HIP(hipMalloc(p, c * unit));
-  *cap = c;
-  return TKV_OK;
-}
 
 constexpr std::uint64_t kRawUnit = 8 + 4 * 4, kDenseUnit = 8 + 5 * 4;
 
@@ -1370,34 +1329,26 @@ SweepArgs carve(WalScratch& s, const std::uint8_t* w, std::uint64_t size, std::u
 
 // The calling thread's device's scratch (created on first use).
 int scratch(WalScratch** out) {
-  int dev = 0;
-  WAL_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return set_error(TKV_INVALID_ARGUMENT, "device index out of range");
-  WalScratch* sp;
-  {
-    std::lock_guard<std::mutex> lk(g_wal_mu);
-    if (!g_wal[dev]) g_wal[dev] = new WalScratch();
-    sp = g_wal[dev];
-  }
+  WalScratch* sp = nullptr;
+  if (int rc = per_device(&sp)) return rc;
   std::lock_guard<std::mutex> lk(sp->mu);
   if (!sp->res) {
-    hipDeviceProp_t prop;
-    WAL_HIP(hipGetDeviceProperties(&prop, dev));
-    sp->ncu = prop.multiProcessorCount;
-    WAL_HIP(hipMalloc(reinterpret_cast<void**>(&sp->inc_p), kMaxFix * sizeof(std::uint32_t)));
-    WAL_HIP(hipMalloc(reinterpret_cast<void**>(&sp->inc_x), kMaxFix * sizeof(std::uint64_t)));
-    WAL_HIP(hipHostMalloc(reinterpret_cast<void**>(&sp->h_inc_p), kMaxFix * sizeof(std::uint32_t), hipHostMallocDefault));
-    WAL_HIP(hipHostMalloc(reinterpret_cast<void**>(&sp->h_inc_x), kMaxFix * sizeof(std::uint64_t), hipHostMallocDefault));
-    WAL_HIP(hipHostMalloc(reinterpret_cast<void**>(&sp->h_task), kMaxFix * 16, hipHostMallocDefault));
-    WAL_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&sp->d_task), sp->h_task, 0));
-    WAL_HIP(hipHostMalloc(reinterpret_cast<void**>(&sp->h_res), kHres * sizeof(std::uint64_t), hipHostMallocDefault));
-    WAL_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&sp->d_hres), sp->h_res, 0));
-    WAL_HIP(hipStreamCreateWithFlags(&sp->st, hipStreamNonBlocking));
-    WAL_HIP(hipStreamCreateWithFlags(&sp->stc, hipStreamNonBlocking));
-    WAL_HIP(hipMalloc(reinterpret_cast<void**>(&sp->res), kResWords * sizeof(unsigned long long)));
-    const std::uint32_t wmax = static_cast<std::uint32_t>(sp->ncu) * kSweepWaves;
-    WAL_HIP(hipMalloc(reinterpret_cast<void**>(&sp->l_cnt), (wmax + 1) * sizeof(std::uint32_t)));
-    WAL_HIP(hipMalloc(reinterpret_cast<void**>(&sp->l_base), (wmax + 1) * sizeof(std::uint64_t)));
+    const int ncu = device_cu_count();
+    if (ncu <= 0) return TKV_IO_ERROR;  // (device_cu_count left the error text)
+    TKV_HIP_RC(hipMalloc(reinterpret_cast<void**>(&sp->inc_p), kMaxFix * sizeof(std::uint32_t)));
+    TKV_HIP_RC(hipMalloc(reinterpret_cast<void**>(&sp->inc_x), kMaxFix * sizeof(std::uint64_t)));
+    TKV_HIP_RC(hipHostMalloc(reinterpret_cast<void**>(&sp->h_inc_p), kMaxFix * sizeof(std::uint32_t), hipHostMallocDefault));
+    TKV_HIP_RC(hipHostMalloc(reinterpret_cast<void**>(&sp->h_inc_x), kMaxFix * sizeof(std::uint64_t), hipHostMallocDefault));
+    TKV_HIP_RC(hipHostMalloc(reinterpret_cast<void**>(&sp->h_task), kMaxFix * 16, hipHostMallocDefault));
+    TKV_HIP_RC(hipHostGetDevicePointer(reinterpret_cast<void**>(&sp->d_task), sp->h_task, 0));
+    TKV_HIP_RC(hipHostMalloc(reinterpret_cast<void**>(&sp->h_res), kHres * sizeof(std::uint64_t), hipHostMallocDefault));
+    TKV_HIP_RC(hipHostGetDevicePointer(reinterpret_cast<void**>(&sp->d_hres), sp->h_res, 0));
+    TKV_HIP_RC(hipStreamCreateWithFlags(&sp->st, hipStreamNonBlocking));
+    TKV_HIP_RC(hipStreamCreateWithFlags(&sp->stc, hipStreamNonBlocking));
+    TKV_HIP_RC(hipMalloc(reinterpret_cast<void**>(&sp->res), kResWords * sizeof(unsigned long long)));
+    const std::uint32_t wmax = static_cast<std::uint32_t>(ncu) * kSweepWaves;
+    TKV_HIP_RC(hipMalloc(reinterpret_cast<void**>(&sp->l_cnt), (wmax + 1) * sizeof(std::uint32_t)));
+    TKV_HIP_RC(hipMalloc(reinterpret_cast<void**>(&sp->l_base), (wmax + 1) * sizeof(std::uint64_t)));
     sp->cap_waves = wmax;
   }
   *out = sp;
@@ -1440,17 +1391,17 @@ int verify_locked(WalScratch& s, const std::uint8_t* w, std::uint64_t size, std:
     else
       hipLaunchKernelGGL((wal_sweep<false, std::uint64_t>), dim3(blocks(W, kSweepWaves)), dim3(kSweepThreads), 0, st, a);
     launch_after(a, s, W, 0, true, true, true, st);
-    WAL_HIP(hipGetLastError());
-    WAL_HIP(hipStreamSynchronize(st));
+    TKV_HIP_RC(hipGetLastError());
+    TKV_HIP_RC(hipStreamSynchronize(st));
     std::uint64_t rounds = 1;
     const bool clean = s.h_res[0] == 0;
     g_rounds.clear();
     // fix-up rounds: every failing boundary is walked again from its true exit (race-free ranges)
     while (s.h_res[0] != 0) {
       const std::uint64_t ninc = std::min<std::uint64_t>(s.h_res[0], kMaxFix);
-      WAL_HIP(hipMemcpyAsync(s.h_inc_p, s.inc_p, ninc * 4, hipMemcpyDeviceToHost, st));
-      WAL_HIP(hipMemcpyAsync(s.h_inc_x, s.inc_x, ninc * 8, hipMemcpyDeviceToHost, st));
-      WAL_HIP(hipStreamSynchronize(st));
+      TKV_HIP_RC(hipMemcpyAsync(s.h_inc_p, s.inc_p, ninc * 4, hipMemcpyDeviceToHost, st));
+      TKV_HIP_RC(hipMemcpyAsync(s.h_inc_x, s.inc_x, ninc * 8, hipMemcpyDeviceToHost, st));
+      TKV_HIP_RC(hipStreamSynchronize(st));
       // failing boundaries (p, exit X; bit 63 of X: p's exit is a fake hop), in region order
       std::vector<std::pair<std::uint32_t, std::uint64_t>> v(ninc);
       for (std::uint64_t i = 0; i < ninc; ++i) v[i] = {s.h_inc_p[i], s.h_inc_x[i]};
@@ -1458,7 +1409,7 @@ int verify_locked(WalScratch& s, const std::uint8_t* w, std::uint64_t size, std:
       if (v[0].first != s.h_res[6]) {  // (more than kMaxFix failed: the list holds an arbitrary part) the first
         const std::uint32_t p0 = static_cast<std::uint32_t>(s.h_res[6]);
         std::uint64_t x0 = 0;
-        WAL_HIP(hipMemcpy(&x0, a.X + p0, 8, hipMemcpyDeviceToHost));
+        TKV_HIP_RC(hipMemcpy(&x0, a.X + p0, 8, hipMemcpyDeviceToHost));
         v.insert(v.begin(), {p0, x0});
         v.resize(std::min<std::size_t>(v.size(), kMaxFix));
       }
@@ -1522,8 +1473,8 @@ int verify_locked(WalScratch& s, const std::uint8_t* w, std::uint64_t size, std:
       const AfterArgs fb{s.l_cnt, W, s.l_base, s.inc_p, s.inc_x, nullptr, 0, false, true, false};
       hipLaunchKernelGGL(wal_after, dim3(blocks(nreg, kFinThreads)), dim3(kFinThreads), 0, st, a, fb);
       hipLaunchKernelGGL(wal_publish, dim3(1), dim3(64), 0, st, a, s.d_hres);
-      WAL_HIP(hipGetLastError());
-      WAL_HIP(hipStreamSynchronize(st));
+      TKV_HIP_RC(hipGetLastError());
+      TKV_HIP_RC(hipStreamSynchronize(st));
       g_rounds[at + 4] = s.h_res[7];
       g_rounds[at + 5] = s.h_res[8];
       ++rounds;
@@ -1552,13 +1503,13 @@ int verify_locked(WalScratch& s, const std::uint8_t* w, std::uint64_t size, std:
         launch_after(a, s, W, 0, false, false, false, st);
         hipLaunchKernelGGL(wal_long_gather, dim3(blocks(nlong, 256)), dim3(256), 0, st, a, s.l_base, W, s.res, d.l_off,
                            d.l_len, d.l_crc, d.l_reg, d.l_meta);
-        WAL_HIP(hipGetLastError());
+        TKV_HIP_RC(hipGetLastError());
         if (int rc = batch_device_impl(kAlgoCrc32, w, d.l_off, d.l_len, nullptr, got, nlong, st)) return rc;
       }
       hipLaunchKernelGGL(wal_reset, dim3(1), dim3(64), 0, st, s.res, static_cast<int>(kResP), static_cast<int>(kResCnt) + 1);
       launch_after(a, s, W, nlong, false, false, true, st);
-      WAL_HIP(hipGetLastError());
-      WAL_HIP(hipStreamSynchronize(st));
+      TKV_HIP_RC(hipGetLastError());
+      TKV_HIP_RC(hipStreamSynchronize(st));
     }
     *n_good = s.h_res[2];
     *stop_offset = s.h_res[3];
@@ -1579,7 +1530,7 @@ int index_locked(WalScratch& s, const std::uint8_t* w, std::uint64_t size, std::
   const std::uint32_t nblk = blocks(nreg, kScanThreads);
   if (int e = grow(&s.idx, &s.cap_idx, nreg, 8 + 8 + 4)) return e;
   if (int e = grow(&s.bsum, &s.cap_bsum, nblk, 8)) return e;
-  if (!s.ires) WAL_HIP(hipMalloc(reinterpret_cast<void**>(&s.ires), kIdxWords * sizeof(unsigned long long)));
+  if (!s.ires) TKV_HIP_RC(hipMalloc(reinterpret_cast<void**>(&s.ires), kIdxWords * sizeof(unsigned long long)));
   // the settled per-region arrays and result words (the long-payload fields are not used here)
   const SweepArgs a = carve(s, w, size, nreg, 0, 0, nullptr);
   IndexArgs x{};
@@ -1592,16 +1543,16 @@ int index_locked(WalScratch& s, const std::uint8_t* w, std::uint64_t size, std::
   x.off32 = d_off32;
   x.cap = cap;
   x.ires = s.ires;
-  WAL_HIP(hipMemsetAsync(s.ires, 0, kIdxWords * sizeof(unsigned long long), st));
+  TKV_HIP_RC(hipMemsetAsync(s.ires, 0, kIdxWords * sizeof(unsigned long long), st));
   hipLaunchKernelGGL(wal_idx_count, dim3(nblk), dim3(kScanThreads), 0, st, a, x);
   hipLaunchKernelGGL(wal_idx_top, dim3(1), dim3(kScanThreads), 0, st, x);
   hipLaunchKernelGGL(wal_idx_base, dim3(nblk), dim3(kScanThreads), 0, st, a, x);
   hipLaunchKernelGGL(wal_idx_emit, dim3(blocks(nreg, kIdxWaves)), dim3(64 * kIdxWaves), 0, st, a, x);
   hipLaunchKernelGGL(wal_idx_max, dim3(nblk), dim3(kScanThreads), 0, st, a, x);
-  WAL_HIP(hipGetLastError());
+  TKV_HIP_RC(hipGetLastError());
   std::uint64_t* h = s.h_res + kHres - kIdxWords;  // (the verify's result words are read; these lie behind them)
-  WAL_HIP(hipMemcpyAsync(h, s.ires, kIdxWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  WAL_HIP(hipStreamSynchronize(st));
+  TKV_HIP_RC(hipMemcpyAsync(h, s.ires, kIdxWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  TKV_HIP_RC(hipStreamSynchronize(st));
   const bool consistent = h[kIdxTotal] == *n_good && h[kIdxIncons] == 0;
 #ifdef TKV_DEBUG
   assert(consistent && "WAL index: the region counts do not add up to the verify's n_good");
@@ -1650,25 +1601,25 @@ int host_image_copy_locked(WalScratch& s, const std::uint8_t* h_wal, std::uint64
   const bool pinned = hipPointerGetAttributes(&attr, h_wal) == hipSuccess && attr.type == hipMemoryTypeHost;
   if (!pinned) (void)hipGetLastError();
   if (pinned) {
-    WAL_HIP(hipMemcpyAsync(s.d_img, h_wal, size, hipMemcpyHostToDevice, s.st));
+    TKV_HIP_RC(hipMemcpyAsync(s.d_img, h_wal, size, hipMemcpyHostToDevice, s.st));
   } else {
     // pageable: host threads fill one pinned slab while the copy engine drains the other
     for (int i = 0; i < 2; ++i) {
       if (!s.slab[i]) {
-        WAL_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.slab[i]), kStageSlab, hipHostMallocDefault));
-        WAL_HIP(hipEventCreateWithFlags(&s.slab_free[i], hipEventDisableTiming));
+        TKV_HIP_RC(hipHostMalloc(reinterpret_cast<void**>(&s.slab[i]), kStageSlab, hipHostMallocDefault));
+        TKV_HIP_RC(hipEventCreateWithFlags(&s.slab_free[i], hipEventDisableTiming));
       }
     }
     int k = 0;
     for (std::uint64_t off = 0; off < size; off += kStageSlab, k ^= 1) {
       const std::uint64_t m = std::min(kStageSlab, size - off);
-      WAL_HIP(hipEventSynchronize(s.slab_free[k]));
+      TKV_HIP_RC(hipEventSynchronize(s.slab_free[k]));
       stage_copy(s.slab[k], h_wal + off, m);
-      WAL_HIP(hipMemcpyAsync(s.d_img + off, s.slab[k], m, hipMemcpyHostToDevice, s.st));
-      WAL_HIP(hipEventRecord(s.slab_free[k], s.st));
+      TKV_HIP_RC(hipMemcpyAsync(s.d_img + off, s.slab[k], m, hipMemcpyHostToDevice, s.st));
+      TKV_HIP_RC(hipEventRecord(s.slab_free[k], s.st));
     }
   }
-  WAL_HIP(hipStreamSynchronize(s.st));
+  TKV_HIP_RC(hipStreamSynchronize(s.st));
   return TKV_OK;
 }
 
@@ -1696,7 +1647,7 @@ int host_index_locked(WalScratch& s, const std::uint8_t* h_wal, std::uint64_t si
                               stop_offset, max_sequence, s.stc, needs_host_walk);
   if (*needs_host_walk || (rc != TKV_OK && rc != TKV_CORRUPTED)) return rc;
   const std::uint64_t n = std::min<std::uint64_t>(*n_good, dcap);
-  if (n) WAL_HIP(hipMemcpy(h_off64, s.d_off, n * 8, hipMemcpyDeviceToHost));
+  if (n) TKV_HIP_RC(hipMemcpy(h_off64, s.d_off, n * 8, hipMemcpyDeviceToHost));
   return rc;
 }
 

@@ -33,14 +33,15 @@
 
 #include "tkv_crc32.h"
 #include "tkv_crc32_device.h"
+#include "tkv_device_util.h"
 #include "tkv_engine.h"
 #include "tkv_wal_device.h"
 #include "tkv_wal_fold.h"
+#include "tkv_wal_layout.h"
 
 namespace tkv {
 namespace {
 
-constexpr std::uint64_t kWalMeta = 26;        // wal.hpp:21-27 kMetadataSize
 constexpr std::uint32_t kEncTile = 4096;      // image bytes per emit tile
 constexpr std::uint32_t kEncPre = 16;         // window bytes in front of the tile's 16-byte granule
 constexpr std::uint32_t kEncOver = 288;       // window bytes past the tile
@@ -97,43 +98,6 @@ __device__ __forceinline__ void wave_sync() {
 
 // ---- size scan --------------------------------------------------------------------------------------
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ std::uint64_t dpp_add64(std::uint64_t x) {
-  const std::uint32_t lo = static_cast<std::uint32_t>(
-      __builtin_amdgcn_update_dpp(0, static_cast<int>(static_cast<std::uint32_t>(x)), CTRL, ROW_MASK, 0xF, false));
-  const std::uint32_t hi = static_cast<std::uint32_t>(
-      __builtin_amdgcn_update_dpp(0, static_cast<int>(static_cast<std::uint32_t>(x >> 32)), CTRL, ROW_MASK, 0xF, false));
-  return x + ((static_cast<std::uint64_t>(hi) << 32) | lo);
-}
-// dev::lane_prefix over u64 values.
-__device__ __forceinline__ std::uint64_t lane_prefix64(std::uint64_t v, std::uint64_t* total) {
-  std::uint64_t x = v;
-  x = dpp_add64<0x111, 0xF>(x);  // row_shr:1
-  x = dpp_add64<0x112, 0xF>(x);  // row_shr:2
-  x = dpp_add64<0x114, 0xF>(x);  // row_shr:4
-  x = dpp_add64<0x118, 0xF>(x);  // row_shr:8
-  x = dpp_add64<0x142, 0xA>(x);  // row_bcast:15 into rows 1 and 3
-  x = dpp_add64<0x143, 0xC>(x);  // row_bcast:31 into rows 2 and 3
-  *total = dev::readlane64(x, 63);
-  return x - v;
-}
-__device__ __forceinline__ std::uint64_t block_prefix64(std::uint64_t v, std::uint64_t* total) {
-  __shared__ std::uint64_t wsum[kScanThreads / 64];
-  std::uint64_t wt;
-  const std::uint64_t pre = lane_prefix64(v, &wt);
-  const std::uint32_t wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63u) == 0) wsum[wv] = wt;
-  __syncthreads();
-  std::uint64_t before = 0, all = 0;
-#pragma unroll
-  for (std::uint32_t k = 0; k < kScanThreads / 64; ++k) {
-    before += k < wv ? wsum[k] : 0u;
-    all += wsum[k];
-  }
-  *total = all;
-  return before + pre;
-}
-
 __device__ __forceinline__ std::uint64_t rec_len64(const EncArgs& a, std::uint64_t i) {
   return 18ull + a.key_len[i] + (a.val_len ? a.val_len[i] : 0u);
 }
@@ -154,7 +118,7 @@ __global__ __launch_bounds__(kScanThreads) void enc_scan(EncArgs a, std::uint64_
     if (i < m) {
       if constexpr (LEVEL0) {
         const std::uint64_t rl = rec_len64(a, i);
-        v[k] = rl + 8u;
+        v[k] = rl + kWalPayload;
         bad |= rl > 0xFFFFFFFFull ? 1u : 0u;
         nlong += (rl > kLaneFold || !a.fused) ? 1u : 0u;
       } else {
@@ -164,7 +128,7 @@ __global__ __launch_bounds__(kScanThreads) void enc_scan(EncArgs a, std::uint64_
     s += v[k];
   }
   std::uint64_t total;
-  std::uint64_t run = block_prefix64(s, &total);
+  std::uint64_t run = dev::block_prefix<std::uint64_t, kScanThreads>(s, &total);
 #pragma unroll
   for (unsigned k = 0; k < kScanItems; ++k) {
     const std::uint64_t i = i0 + k;
@@ -199,14 +163,14 @@ __global__ __launch_bounds__(kScanThreads) void enc_finish(EncArgs a, const std:
   a.off[i] = o;
   if (a.rec_off) a.rec_off[i] = o;
   const std::uint64_t rl = rec_len64(a, i);
-  const std::uint64_t e = o + rl + 8u;
+  const std::uint64_t e = o + rl + kWalPayload;
   for (std::uint64_t t = o / kEncTile; t * kEncTile < e; ++t) {  // one writer per word: records tile the image
     if (o <= t * kEncTile) a.tile_first[2u * t] = static_cast<std::uint32_t>(i);
     if (e >= (t + 1u) * kEncTile || i + 1u == a.n) a.tile_first[2u * t + 1u] = static_cast<std::uint32_t>(i);
   }
   if (rl > kLaneFold || !a.fused) {
     const unsigned long long k = atomicAdd(&a.cnt[kCntCursor], 1ull);
-    a.l_off[k] = o + 8u;
+    a.l_off[k] = o + kWalPayload;
     a.l_len[k] = static_cast<std::uint32_t>(rl);
     a.l_idx[k] = static_cast<std::uint32_t>(i);
   }
@@ -216,7 +180,7 @@ __global__ __launch_bounds__(kScanThreads) void enc_stamp(EncArgs a, std::uint64
   const std::uint64_t k = blockIdx.x * static_cast<std::uint64_t>(kScanThreads) + threadIdx.x;
   if (k >= nlong) return;
   const std::uint32_t c = a.l_crc[k];
-  std::uint8_t* p = a.img + (a.l_off[k] - 4u);
+  std::uint8_t* p = a.img + (a.l_off[k] - (kWalPayload - kWalCrc));
   p[0] = static_cast<std::uint8_t>(c);
   p[1] = static_cast<std::uint8_t>(c >> 8);
   p[2] = static_cast<std::uint8_t>(c >> 16);
@@ -426,9 +390,9 @@ __device__ __forceinline__ void emit_tile(const EncArgs& a, std::uint8_t* win, c
     const std::uint64_t ro = act ? r.ro : ts, seq = r.seq, ko = r.ko, vo = r.vo;
     const std::uint32_t kl = r.kl, vl = r.vl, op = r.op, tomb = r.tomb;
     const std::uint32_t rl = 18u + kl + vl;  // fits: the host checked the scan's flag
-    const std::uint64_t size = static_cast<std::uint64_t>(rl) + 8u;
+    const std::uint64_t size = static_cast<std::uint64_t>(rl) + kWalPayload;
     // folded here: short, and a byte of its CRC field lies in the tile (it starts before te)
-    const bool fold = act && a.fused && rl <= kLaneFold && ro + 8u > ts;
+    const bool fold = act && a.fused && rl <= kLaneFold && ro + kWalPayload > ts;
     const std::uint64_t clo = fold ? ro : (ro > ts ? ro : ts);
     const std::uint64_t chi = fold ? ro + size : (ro + size < te ? ro + size : te);
     // window offset of the record's byte 0 (meaningful when a header byte is laid out)
@@ -461,10 +425,10 @@ __device__ __forceinline__ void emit_tile(const EncArgs& a, std::uint8_t* win, c
     wave_sync();
     // the lane fold (fold_raw plus the initial register's term), its CRC into the window's field
     const std::uint32_t L = fold ? rl : 0u;
-    const std::uint32_t c = fold_raw(win, tab, kc, fold ? hw + 8u : kEncPre, L) ^ inj[L] ^ 0xFFFFFFFFu;
+    const std::uint32_t c = fold_raw(win, tab, kc, fold ? hw + kWalPayload : kEncPre, L) ^ inj[L] ^ 0xFFFFFFFFu;
     if (fold) {
 #pragma unroll
-      for (std::uint32_t b = 0; b < 4u; ++b) win[hw + 4u + b] = static_cast<std::uint8_t>(c >> (8u * b));
+      for (std::uint32_t b = 0; b < 4u; ++b) win[hw + kWalCrc + b] = static_cast<std::uint8_t>(c >> (8u * b));
       if (ro >= ts && a.crc) a.crc[i] = c;
     }
   }
@@ -542,49 +506,19 @@ struct EncScratch {
   }
 };
 
-std::mutex g_enc_mu;
-EncScratch* g_enc[64] = {};
 std::atomic<int> g_enc_fused{1};
 // What the calling thread's last device encode did (tkv_debug_wal_encode_last).
 thread_local std::uint64_t g_enc_last[4] = {0, 0, 0, 0};
 
-#define ENC_HIP(call)                                                            \
-  do {                                                                           \
-    hipError_t e_ = (call);                                                      \
-    if (e_ != hipSuccess) return set_error(TKV_IO_ERROR, hipGetErrorString(e_)); \
-  } while (0)
-
-unsigned blocks(std::uint64_t n, std::uint64_t t) { return static_cast<unsigned>((n + t - 1) / t); }
-
-int grow(void** p, std::uint64_t* cap, std::uint64_t want, std::uint64_t unit) {
-  if (want <= *cap) return TKV_OK;
-  const std::uint64_t c = std::max<std::uint64_t>(want, 2 * *cap);
-  ENC_HIP(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  ENC_HIP(hipMalloc(p, c * unit));
-  *cap = c;
-  return TKV_OK;
-}
-
 int scratch(EncScratch** out) {
-  int dev = 0;
-  ENC_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return set_error(TKV_INVALID_ARGUMENT, "device index out of range");
-  EncScratch* sp;
-  {
-    std::lock_guard<std::mutex> lk(g_enc_mu);
-    if (!g_enc[dev]) g_enc[dev] = new EncScratch();
-    sp = g_enc[dev];
-  }
+  EncScratch* sp = nullptr;
+  if (int rc = per_device(&sp)) return rc;
   std::lock_guard<std::mutex> lk(sp->mu);
   if (!sp->cnt) {
-    hipDeviceProp_t prop;
-    ENC_HIP(hipGetDeviceProperties(&prop, dev));
-    sp->ncu = prop.multiProcessorCount;
-    ENC_HIP(hipHostMalloc(reinterpret_cast<void**>(&sp->h_res), kEncHres * sizeof(std::uint64_t), hipHostMallocDefault));
-    ENC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&sp->d_hres), sp->h_res, 0));
-    ENC_HIP(hipMalloc(reinterpret_cast<void**>(&sp->cnt), kCntWords * sizeof(unsigned long long)));
+    sp->ncu = device_cu_count();
+    TKV_HIP_RC(hipHostMalloc(reinterpret_cast<void**>(&sp->h_res), kEncHres * sizeof(std::uint64_t), hipHostMallocDefault));
+    TKV_HIP_RC(hipHostGetDevicePointer(reinterpret_cast<void**>(&sp->d_hres), sp->h_res, 0));
+    TKV_HIP_RC(hipMalloc(reinterpret_cast<void**>(&sp->cnt), kCntWords * sizeof(unsigned long long)));
   }
   *out = sp;
   return TKV_OK;
@@ -609,14 +543,14 @@ int encode_locked(EncScratch& s, EncArgs a, std::uint64_t cap, std::uint64_t* im
   lv[0] = a.off;
   lv[1] = static_cast<std::uint64_t*>(s.sums);
   for (int k = 2; k <= levels; ++k) lv[k] = lv[k - 1] + m[k - 1];
-  ENC_HIP(hipMemsetAsync(s.cnt, 0, kCntWords * sizeof(unsigned long long), st));
+  TKV_HIP_RC(hipMemsetAsync(s.cnt, 0, kCntWords * sizeof(unsigned long long), st));
   s.h_res[3] = 0;
   hipLaunchKernelGGL(enc_scan<true>, dim3(static_cast<unsigned>(m[1])), dim3(kScanThreads), 0, st, a, lv[0], m[0], lv[1]);
   for (int k = 1; k < levels; ++k)
     hipLaunchKernelGGL(enc_scan<false>, dim3(static_cast<unsigned>(m[k + 1])), dim3(kScanThreads), 0, st, a, lv[k], m[k], lv[k + 1]);
   hipLaunchKernelGGL(enc_publish, dim3(1), dim3(64), 0, st, lv[levels], s.cnt, s.d_hres);
-  ENC_HIP(hipGetLastError());
-  ENC_HIP(hipStreamSynchronize(st));
+  TKV_HIP_RC(hipGetLastError());
+  TKV_HIP_RC(hipStreamSynchronize(st));
   if (s.h_res[3] != 1) return set_error(TKV_IO_ERROR, "WAL encode: the size scan left no result");
   const std::uint64_t total = s.h_res[0], nlong = s.h_res[2];
   if (s.h_res[1]) return set_error(TKV_INVALID_ARGUMENT, "WAL encode: 18 + key_len + val_len does not fit u32");
@@ -637,16 +571,16 @@ int encode_locked(EncScratch& s, EncArgs a, std::uint64_t cap, std::uint64_t* im
   hipLaunchKernelGGL(enc_finish, dim3(blocks(a.n, kScanThreads)), dim3(kScanThreads), 0, st, a,
                      levels > 1 ? lv[1] : static_cast<const std::uint64_t*>(nullptr));
   const std::uint64_t want = (a.ntiles + kEncWaves - 1u) / kEncWaves;
-  const unsigned grid = static_cast<unsigned>(std::min<std::uint64_t>(want, static_cast<std::uint64_t>(std::max(1, s.ncu))));
+  const unsigned grid = static_cast<unsigned>(std::min<std::uint64_t>(want, std::max(1, s.ncu)));
   a.nwaves = grid * kEncWaves;
   hipLaunchKernelGGL(enc_emit, dim3(grid), dim3(kEncThreads), 0, st, a);
-  ENC_HIP(hipGetLastError());
+  TKV_HIP_RC(hipGetLastError());
   if (nlong) {
     if (int rc = batch_device_impl(kAlgoCrc32, a.img, a.l_off, a.l_len, nullptr, a.l_crc, nlong, st)) return rc;
     hipLaunchKernelGGL(enc_stamp, dim3(blocks(nlong, kScanThreads)), dim3(kScanThreads), 0, st, a, nlong);
-    ENC_HIP(hipGetLastError());
+    TKV_HIP_RC(hipGetLastError());
   }
-  ENC_HIP(hipStreamSynchronize(st));
+  TKV_HIP_RC(hipStreamSynchronize(st));
   g_enc_last[0] = a.n - nlong;
   g_enc_last[1] = nlong;
   g_enc_last[2] = a.nwaves;

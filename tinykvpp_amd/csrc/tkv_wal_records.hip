@@ -24,17 +24,17 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdint>
 
 #include "tkv_crc32.h"
 #include "tkv_crc32_device.h"
+#include "tkv_device_util.h"
 #include "tkv_engine.h"
+#include "tkv_wal_layout.h"
 
 namespace tkv {
 namespace {
 
-constexpr std::uint32_t kRecMeta = 26;  // wal.hpp kMetadataSize: 8-byte header + op, seq, tombstone, key/value lengths
 // The granule kernel uses the 128 KiB table image with one 1024-thread workgroup per CU (narrow
 // windows on the 64 KiB image with two 768-thread workgroups measured 3 % slower,
 // profiles/r4/lanes16/rec_probe_rec16.jsonl).
@@ -134,17 +134,17 @@ __global__ __launch_bounds__(kRecThreadsN) void wal_rec_lanes(RecArgs a, const D
     const std::uintptr_t p = w0 + off;
     std::uint32_t d[ND];
     rec_dwords<NG>(q[slot], static_cast<std::uint32_t>(p & 15u), d);
-    const std::uint32_t rlen = d[0], stored = d[1];
-    const std::uint32_t klen = __builtin_amdgcn_alignbyte(d[5], d[4], 2u);
-    const std::uint32_t vlen = __builtin_amdgcn_alignbyte(d[6], d[5], 2u);
+    const std::uint32_t rlen = d[0], stored = d[kWalCrc / 4];
+    const std::uint32_t klen = __builtin_amdgcn_alignbyte(d[kWalKeyLen / 4 + 1], d[kWalKeyLen / 4], kWalKeyLen % 4);
+    const std::uint32_t vlen = __builtin_amdgcn_alignbyte(d[kWalValLen / 4 + 1], d[kWalValLen / 4], kWalValLen % 4);
     const std::uint64_t left = off < a.size ? a.size - off : 0u;
-    const bool len_ok = left >= kRecMeta && static_cast<std::uint64_t>(rlen) + 8u <= left;  // wal.cpp:68, :80
+    const bool len_ok = left >= kWalMeta && static_cast<std::uint64_t>(rlen) + kWalPayload <= left;  // wal.cpp:68, :80
     const std::uint32_t L = live && len_ok ? rlen : 0u;
-    std::uint32_t c = rec_fold<NPAY>(lds, kc, d + 2, L < 4u * NPAY ? L : 4u * NPAY, 0xFFFFFFFFu);
+    std::uint32_t c = rec_fold<NPAY>(lds, kc, d + kWalPayload / 4, L < 4u * NPAY ? L : 4u * NPAY, 0xFFFFFFFFu);
     // payloads longer than the window: 64 bytes at a time from fresh granules, the register carried
     for (std::uint32_t done = 4u * NPAY; __ballot(L > done) != 0; done += 64u) {
       const std::uint32_t m = L > done ? std::min(L - done, 64u) : 0u;
-      const std::uintptr_t ps = p + 8u + done;
+      const std::uintptr_t ps = p + kWalPayload + done;
       const std::uintptr_t al = ps & ~static_cast<std::uintptr_t>(15);
       uint4 g[dev::kLaneGran];
 #pragma unroll
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(kRecThreadsN) void wal_rec_lanes(RecArgs a, const D
       c = rec_fold<16>(lds, kc, e17, m, c);
     }
     const std::uint32_t crc = c ^ 0xFFFFFFFFu;
-    const bool kv_ok = static_cast<std::uint64_t>(klen) + vlen + (kRecMeta - 8u) <= rlen;  // wal.cpp:118-121
+    const bool kv_ok = static_cast<std::uint64_t>(klen) + vlen + (kWalMeta - kWalPayload) <= rlen;  // wal.cpp:118-121
     if (live && a.crc) a.crc[b] = len_ok ? crc : 0u;
     if (live && (!len_ok || crc != stored || !kv_ok)) atomicMin(a.first_bad, static_cast<unsigned long long>(b));
   };
@@ -191,26 +191,6 @@ __global__ __launch_bounds__(kRecThreadsN) void wal_rec_lanes(RecArgs a, const D
 // image; 12 waves x (2 x 3 KiB + 2 x 256 B) of buffers.
 constexpr unsigned kRecLdsThreads = 768;
 constexpr std::uint32_t kRecLdsBuf = 3072;
-__device__ __forceinline__ std::uint32_t umin32(std::uint32_t x, std::uint32_t y) { return x < y ? x : y; }
-__device__ __forceinline__ std::uint32_t umax32(std::uint32_t x, std::uint32_t y) { return x > y ? x : y; }
-__device__ __forceinline__ std::uint32_t wave_min_u32(std::uint32_t v) {
-  v = umin32(v, static_cast<std::uint32_t>(__builtin_amdgcn_update_dpp(~0u, v, 0xB1, 0xF, 0xF, false)));
-  v = umin32(v, static_cast<std::uint32_t>(__builtin_amdgcn_update_dpp(~0u, v, 0x4E, 0xF, 0xF, false)));
-  v = umin32(v, static_cast<std::uint32_t>(__builtin_amdgcn_update_dpp(~0u, v, 0x141, 0xF, 0xF, false)));
-  v = umin32(v, static_cast<std::uint32_t>(__builtin_amdgcn_update_dpp(~0u, v, 0x140, 0xF, 0xF, false)));
-  v = umin32(v, static_cast<std::uint32_t>(__builtin_amdgcn_update_dpp(~0u, v, 0x142, 0xA, 0xF, false)));
-  v = umin32(v, static_cast<std::uint32_t>(__builtin_amdgcn_update_dpp(~0u, v, 0x143, 0xC, 0xF, false)));
-  return __builtin_amdgcn_readlane(v, 63);
-}
-__device__ __forceinline__ std::uint32_t wave_max_u32(std::uint32_t v) {
-  v = umax32(v, static_cast<std::uint32_t>(__builtin_amdgcn_update_dpp(0u, v, 0xB1, 0xF, 0xF, false)));
-  v = umax32(v, static_cast<std::uint32_t>(__builtin_amdgcn_update_dpp(0u, v, 0x4E, 0xF, 0xF, false)));
-  v = umax32(v, static_cast<std::uint32_t>(__builtin_amdgcn_update_dpp(0u, v, 0x141, 0xF, 0xF, false)));
-  v = umax32(v, static_cast<std::uint32_t>(__builtin_amdgcn_update_dpp(0u, v, 0x140, 0xF, 0xF, false)));
-  v = umax32(v, static_cast<std::uint32_t>(__builtin_amdgcn_update_dpp(0u, v, 0x142, 0xA, 0xF, false)));
-  v = umax32(v, static_cast<std::uint32_t>(__builtin_amdgcn_update_dpp(0u, v, 0x143, 0xC, 0xF, false)));
-  return __builtin_amdgcn_readlane(v, 63);
-}
 
 template <int NG>
 __global__ __launch_bounds__(kRecLdsThreads) void wal_rec_lds(RecArgs a, const DeviceTables* tabs) {
@@ -251,7 +231,7 @@ __global__ __launch_bounds__(kRecLdsThreads) void wal_rec_lds(RecArgs a, const D
   auto plan = [&](std::uint32_t j) {  // step j's offsets have landed: copy its span if it fits
     const std::uint32_t k = j & 1u;
     const std::uint32_t off = dev::lds_at(lds, offs0 + k * 256u + 4u * lane);
-    const std::uint32_t mn = wave_min_u32(off), mx = wave_max_u32(off);
+    const std::uint32_t mn = dev::wave_min(off), mx = dev::wave_max(off);
     const std::uintptr_t al = (w0 + mn) & ~static_cast<std::uintptr_t>(15);
     const std::uint32_t o = static_cast<std::uint32_t>(w0 + mn - al);
     const bool staged = static_cast<std::uint64_t>(mx - mn) + o + 16u * NG <= kRecLdsBuf;
@@ -322,17 +302,17 @@ __global__ __launch_bounds__(kRecLdsThreads) void wal_rec_lds(RecArgs a, const D
       for (int i = 0; i < ND; ++i) d[i] = e[i];
     }
     d[ND] = 0u;
-    const std::uint32_t rlen = d[0], stored = d[1];
-    const std::uint32_t klen = __builtin_amdgcn_alignbyte(d[5], d[4], 2u);
-    const std::uint32_t vlen = __builtin_amdgcn_alignbyte(d[6], d[5], 2u);
+    const std::uint32_t rlen = d[0], stored = d[kWalCrc / 4];
+    const std::uint32_t klen = __builtin_amdgcn_alignbyte(d[kWalKeyLen / 4 + 1], d[kWalKeyLen / 4], kWalKeyLen % 4);
+    const std::uint32_t vlen = __builtin_amdgcn_alignbyte(d[kWalValLen / 4 + 1], d[kWalValLen / 4], kWalValLen % 4);
     const std::uint64_t left = off < a.size ? a.size - off : 0u;
-    const bool len_ok = left >= kRecMeta && static_cast<std::uint64_t>(rlen) + 8u <= left;  // wal.cpp:68, :80
+    const bool len_ok = left >= kWalMeta && static_cast<std::uint64_t>(rlen) + kWalPayload <= left;  // wal.cpp:68, :80
     const std::uint32_t L = live && len_ok ? rlen : 0u;
-    std::uint32_t c = rec_fold<NPAY>(lds, kc, d + 2, L < 4u * NPAY ? L : 4u * NPAY, 0xFFFFFFFFu);
+    std::uint32_t c = rec_fold<NPAY>(lds, kc, d + kWalPayload / 4, L < 4u * NPAY ? L : 4u * NPAY, 0xFFFFFFFFu);
     // payloads longer than the window: 64 bytes at a time from fresh granules, the register carried
     for (std::uint32_t done = 4u * NPAY; __ballot(L > done) != 0; done += 64u) {
       const std::uint32_t m = L > done ? std::min(L - done, 64u) : 0u;
-      const std::uintptr_t ps = p + 8u + done;
+      const std::uintptr_t ps = p + kWalPayload + done;
       const std::uintptr_t al = ps & ~static_cast<std::uintptr_t>(15);
       uint4 g[dev::kLaneGran];
 #pragma unroll
@@ -346,27 +326,14 @@ __global__ __launch_bounds__(kRecLdsThreads) void wal_rec_lds(RecArgs a, const D
       c = rec_fold<16>(lds, kc, e17, m, c);
     }
     const std::uint32_t crc = c ^ 0xFFFFFFFFu;
-    const bool kv_ok = static_cast<std::uint64_t>(klen) + vlen + (kRecMeta - 8u) <= rlen;  // wal.cpp:118-121
+    const bool kv_ok = static_cast<std::uint64_t>(klen) + vlen + (kWalMeta - kWalPayload) <= rlen;  // wal.cpp:118-121
     if (live && a.crc) a.crc[b] = len_ok ? crc : 0u;
     if (live && (!len_ok || crc != stored || !kv_ok)) atomicMin(a.first_bad, static_cast<unsigned long long>(b));
   }
 }
 
-int cu_count() {
-  static std::atomic<int> cached[64] = {};  // (concurrent first calls store the same value)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-  int c = cached[dev].load(std::memory_order_relaxed);
-  if (c == 0) {
-    if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    cached[dev].store(c, std::memory_order_relaxed);
-  }
-  return c;
-}
-
 // The record check over n records (first_bad preset to n by the caller's stream order).
-void launch_records(RecArgs a, std::uint32_t max_payload, int ncu, const DeviceTables* tabs, hipStream_t st) {
-  const std::uint64_t steps = (a.n + 63) / 64;
+void launch_records(RecArgs a, std::uint32_t max_payload, unsigned ncu, const DeviceTables* tabs, hipStream_t st) {
   // window: NG granules hold the header, the key/value lengths and a first fold of 16 NG - 28 payload
   // bytes at any alignment (36-byte payloads: 4 granules; 68: 6; 100: 8); longer ones continue 64 bytes
   // at a time. Records are latency-bound like the lane kernel (profiles/r4/rec_check/).
@@ -377,19 +344,15 @@ void launch_records(RecArgs a, std::uint32_t max_payload, int ncu, const DeviceT
   // of payload; 36-byte records (28-byte payloads) 2813 -> 2591, where the per-step cost (span
   // reduction, copy, full wait) outweighs what the copy saves, so shorter payloads keep wal_rec_lanes.
   if (ng <= 5 && max_payload >= 32u) {
-    constexpr std::uint64_t waves = kRecLdsThreads / 64;
-    const std::uint64_t grid =
-        std::max<std::uint64_t>(1, std::min<std::uint64_t>(static_cast<std::uint64_t>(ncu), (steps + waves - 1) / waves));
-    a.nwaves = static_cast<std::uint32_t>(grid * waves);
-    if (ng == 4) hipLaunchKernelGGL((wal_rec_lds<4>), dim3(static_cast<unsigned>(grid)), dim3(kRecLdsThreads), 0, st, a, tabs);
-    else hipLaunchKernelGGL((wal_rec_lds<5>), dim3(static_cast<unsigned>(grid)), dim3(kRecLdsThreads), 0, st, a, tabs);
+    const unsigned grid = wave_grid(a.n, ncu, kRecLdsThreads / 64);
+    a.nwaves = grid * (kRecLdsThreads / 64);
+    if (ng == 4) hipLaunchKernelGGL((wal_rec_lds<4>), dim3(grid), dim3(kRecLdsThreads), 0, st, a, tabs);
+    else hipLaunchKernelGGL((wal_rec_lds<5>), dim3(grid), dim3(kRecLdsThreads), 0, st, a, tabs);
     return;
   }
-  const std::uint64_t waves = kRecThreadsN / 64;
-  const std::uint64_t grid =
-      std::max<std::uint64_t>(1, std::min<std::uint64_t>(static_cast<std::uint64_t>(ncu), (steps + waves - 1) / waves));
-  a.nwaves = static_cast<std::uint32_t>(grid * waves);
-  const dim3 g(static_cast<unsigned>(grid)), b(kRecThreadsN);
+  const unsigned grid = wave_grid(a.n, ncu, kRecThreadsN / 64);
+  a.nwaves = grid * (kRecThreadsN / 64);
+  const dim3 g(grid), b(kRecThreadsN);
   switch (ng) {
     case 4: hipLaunchKernelGGL((wal_rec_lanes<4, 0>), g, b, 0, st, a, tabs); break;
     case 5: hipLaunchKernelGGL((wal_rec_lanes<5, 3>), g, b, 0, st, a, tabs); break;
@@ -410,13 +373,13 @@ extern "C" int tkv_wal_check_records_device(const uint8_t* d_img, uint64_t size,
   if (size > 0xFFFFFFFFull + 1ull) return set_error(TKV_INVALID_ARGUMENT, "image larger than 4 GiB (u32 offsets)");
   const DeviceTables* tabs = device_tables(kAlgoCrc32);
   if (!tabs) return TKV_IO_ERROR;
-  const int ncu = cu_count();
+  const int ncu = device_cu_count();
   if (ncu <= 0) return set_error(TKV_IO_ERROR, "no device");
   auto st = static_cast<hipStream_t>(stream);
   auto* fb = reinterpret_cast<unsigned long long*>(d_first_bad);
   // no records past an empty image can be good: the first record (if any) is the first bad one
   hipLaunchKernelGGL(rec_init, dim3(1), dim3(1), 0, st, fb, size ? n : 0);
-  if (n && size) launch_records(RecArgs{d_img, size, d_rec_off, n, d_crc, fb, 0}, max_payload, ncu, tabs, st);
+  if (n && size) launch_records(RecArgs{d_img, size, d_rec_off, n, d_crc, fb, 0}, max_payload, static_cast<unsigned>(ncu), tabs, st);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(TKV_IO_ERROR, hipGetErrorString(e));
   return TKV_OK;
