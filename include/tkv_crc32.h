@@ -221,6 +221,64 @@ int tkv_wal_encode(const uint8_t *h_keys, const uint64_t *h_key_off, const uint3
                    uint64_t n, uint8_t *h_img, uint64_t cap, uint64_t *h_rec_off, uint32_t *h_crc,
                    uint64_t *img_size);
 
+/* ---- WAL batched decode (the inverse of the encode above) --------------------------------------- */
+
+#define TKV_WAL_DECODE_KEY_VIEWS 1u   /* keys stay in the image */
+#define TKV_WAL_DECODE_VAL_VIEWS 2u   /* values stay in the image */
+
+/* The fields wal_entry::decode (wal.cpp:98-127) takes out of a record, for n records of an image in
+ * DEVICE memory whose start offsets are known, in the columnar form tkv_wal_encode_device takes. Record
+ * i starts at d_img + rec_off[i]; exactly one of d_rec_off64 (the list tkv_wal_index_device writes) and
+ * d_rec_off32 (size <= 4 GiB) is non-NULL. The offsets need not be in chain order, may repeat, and the
+ * records may overlap one another: this is a gather.
+ * Columns (device, n entries, each nullable and then skipped): op[i] = byte 8 and tomb[i] = byte 17 as
+ * stored, seq[i] = u64 LE at byte 9, key_len[i] / val_len[i] = u32 LE at bytes 18 / 22.
+ * Key arena: record i's key is image bytes [rec_off[i] + 26, + key_len[i]). Without
+ * TKV_WAL_DECODE_KEY_VIEWS the keys are written back to back in batch order into d_keys, key_off[i] is
+ * the exclusive u64 prefix sum of key_len and *keys_size the sum. With it nothing is copied, d_keys /
+ * keys_cap are ignored, key_off[i] = rec_off[i] + 26 and *keys_size is still the sum. Value arena: the
+ * same with TKV_WAL_DECODE_VAL_VIEWS, d_vals and val_off[i]; the source is rec_off[i] + 26 +
+ * key_len[i]. Bytes of a record behind its value (record_len > 18 + key_len + val_len) are ignored, as
+ * the reference ignores them (wal.cpp:118-125).
+ * In either mode the outputs are valid tkv_wal_encode_device inputs with keys / vals = the arena, or
+ * = d_img for a views arena; when every record has the shape the reference encoder writes (record_len
+ * == 18 + key_len + val_len, tombstone byte 0 or 1) encoding them reproduces the records byte for
+ * byte, CRC field included.
+ * Per record, wal_entry::decode's structural checks in 64-bit arithmetic: at least 26 bytes left at
+ * rec_off[i] (wal.cpp:68), record_len + 8 within the image (:83), 18 + key_len + val_len <= record_len
+ * (:118-121). NO CHECKSUM IS COMPUTED: that is the business of tkv_wal_index[_device] and
+ * tkv_wal_check_records_device, which produce or check the offsets this call takes. No byte outside
+ * [d_img, d_img + size) is read for any input, and the lengths of a record that fails a check are never
+ * used as copy lengths. If any record fails: TKV_CORRUPTED, *first_bad = the smallest failing index,
+ * *keys_size = *vals_size = 0 and nothing is written to any output array (a caller that wants the
+ * prefix calls again with n = *first_bad). Otherwise *first_bad = n.
+ * *keys_size > keys_cap for a copied arena, or the same for values: TKV_BUFFER_OVERFLOW; both sizes are
+ * reported and nothing is written to any output array, columns included (caps of 0 with NULL arenas is
+ * the sizing call). A copied arena whose total is 0 may be NULL. d_keys / d_vals may have any byte
+ * alignment; no byte outside [d_keys, d_keys + *keys_size) and [d_vals, d_vals + *vals_size) is written
+ * or read-modify-written; destinations do not overlap the image.
+ * TKV_INVALID_ARGUMENT, decided before any device work: n > 2^32 - 1, both or neither offset array,
+ * d_rec_off32 with size > 4 GiB, unknown flag bits, NULL d_img with n > 0, NULL keys_size / vals_size /
+ * first_bad. n == 0: TKV_OK, sizes 0, *first_bad = 0, nothing else touched.
+ * Synchronous on `stream` (the host needs the totals and first_bad before the emit); with no usable GPU
+ * it returns TKV_IO_ERROR. */
+int tkv_wal_decode_device(const uint8_t *d_img, uint64_t size, const uint64_t *d_rec_off64,
+                          const uint32_t *d_rec_off32, uint64_t n, uint32_t flags, uint8_t *d_op, uint8_t *d_tomb,
+                          uint64_t *d_seq, uint64_t *d_key_off, uint32_t *d_key_len, uint64_t *d_val_off,
+                          uint32_t *d_val_len, uint8_t *d_keys, uint64_t keys_cap, uint8_t *d_vals,
+                          uint64_t vals_cap, uint64_t *keys_size, uint64_t *vals_size, uint64_t *first_bad,
+                          void *stream);
+
+/* The same contract with every argument in HOST memory (u64 offsets only): the decode for an image the
+ * caller holds on the host, paired with tkv_wal_index. It is NOT a fallback of the device call: the
+ * field extraction and the arena copies run on host threads, no GPU is used and no checksum is
+ * computed. */
+int tkv_wal_decode_host(const uint8_t *h_img, uint64_t size, const uint64_t *h_rec_off64, uint64_t n, uint32_t flags,
+                        uint8_t *h_op, uint8_t *h_tomb, uint64_t *h_seq, uint64_t *h_key_off, uint32_t *h_key_len,
+                        uint64_t *h_val_off, uint32_t *h_val_len, uint8_t *h_keys, uint64_t keys_cap,
+                        uint8_t *h_vals, uint64_t vals_cap, uint64_t *keys_size, uint64_t *vals_size,
+                        uint64_t *first_bad);
+
 /* ---- SSTable data-block stamping (the format is defined here) ----------- */
 
 /* The reference writes sstable_data_block_header::crc32_ = 0 (sstable_writer.cpp:138-144) and never
@@ -409,6 +467,14 @@ void tkv_debug_wal_encode_last(uint64_t out[4]);
  * then every record is stamped by the read-back route (kept so one process can run both routes on the
  * same inputs). Returns the previous setting. Default 1. */
 int tkv_debug_set_wal_encode_fused(int enable);
+/* Geometry of tkv_wal_decode_device: out[0] = arena bytes per emit tile, out[1] = records per workgroup
+ * of the length scans, out[2] = the longest span one lane copies (longer ones are copied by the whole
+ * wave), out[3] = number of scan levels (for 2^32 - 1 records). */
+void tkv_debug_wal_decode_geometry(uint64_t out[4]);
+/* What the calling thread's last tkv_wal_decode_device did: out[0] = emit waves for the key arena,
+ * out[1] = emit waves for the value arena (0 for a views or empty arena), out[2] = key bytes, out[3] =
+ * value bytes (all 0 when it wrote nothing). */
+void tkv_debug_wal_decode_last(uint64_t out[4]);
 
 
 #ifdef __cplusplus

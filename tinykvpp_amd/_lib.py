@@ -59,6 +59,10 @@ SIGNATURES = {
                                      ctypes.POINTER(_u64), _vp]),
     "tkv_wal_encode": (_int, [_u8p, _vp, _vp, _u8p, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u8p, _u64, _vp, _vp,
                               ctypes.POINTER(_u64)]),
+    "tkv_wal_decode_device": (_int, [_u8p, _u64, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u8p, _u64, _u8p,
+                                     _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64), _vp]),
+    "tkv_wal_decode_host": (_int, [_u8p, _u64, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u8p, _u64, _u8p, _u64,
+                                   ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "tkv_wal_check_records_device": (_int, [_u8p, _u64, _vp, _u64, _u32, _vp, _vp, _vp]),
     "tkv_fill_synthetic_uniform": (_int, [_u8p, _u64, _u64, _u64, _u64, _u64, _vp]),
     "tkv_fill_synthetic_blocks": (_int, [_u8p, _vp, _vp, _u64, _u64, _u64, _vp]),
@@ -87,6 +91,8 @@ SIGNATURES = {
     "tkv_debug_wal_encode_geometry": (None, [_vp]),
     "tkv_debug_wal_encode_last": (None, [_vp]),
     "tkv_debug_set_wal_encode_fused": (_int, [_int]),
+    "tkv_debug_wal_decode_geometry": (None, [_vp]),
+    "tkv_debug_wal_decode_last": (None, [_vp]),
     "tkv_debug_wal_chain": (_sz, [_u8p, _u64, _vp, _sz, ctypes.POINTER(_u64), ctypes.POINTER(_int)]),
     "tkv_debug_wal_last": (None, [_vp]),
     "tkv_debug_wal_rounds": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
@@ -105,7 +111,9 @@ SIGNATURES = {
 # symbols an older build may lack (tools/ab_lib.py loads earlier builds for A/B runs)
 OPTIONAL = {"tkv_build_id", "tkv_wal_index_device", "tkv_wal_index", "tkv_debug_set_wal_round_budget",
             "tkv_debug_set_packed_fold", "tkv_wal_encode_device", "tkv_wal_encode", "tkv_debug_wal_encode_layout",
-            "tkv_debug_wal_encode_geometry", "tkv_debug_wal_encode_last", "tkv_debug_set_wal_encode_fused"}
+            "tkv_debug_wal_encode_geometry", "tkv_debug_wal_encode_last", "tkv_debug_set_wal_encode_fused",
+            "tkv_wal_decode_device", "tkv_wal_decode_host", "tkv_debug_wal_decode_geometry",
+            "tkv_debug_wal_decode_last"}
 
 _lib = None
 

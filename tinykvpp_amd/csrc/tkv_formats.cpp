@@ -7,6 +7,7 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <thread>
@@ -510,6 +511,117 @@ size_t tkv_debug_wal_encode_layout(const uint8_t* h_keys, const uint64_t* h_key_
   bool laid = false;
   if (encode_host_layout(in, h_img, cap, img_size, off, &laid) != TKV_OK || !laid) return 0;
   return static_cast<size_t>(n);
+}
+
+}  // extern "C"
+
+namespace {
+// ---- WAL batched decode (wal.cpp:98-127 for a record list) -------------------------------------------
+
+// The argument checks both entry points share; *done is set when the call is finished (n == 0).
+int decode_check(const void* img, std::uint64_t size, const void* off64, const void* off32, std::uint64_t n,
+                 std::uint32_t flags, std::uint64_t* keys_size, std::uint64_t* vals_size, std::uint64_t* first_bad, bool* done) {
+  *done = false;
+  if (!ptr_ok(keys_size) || !ptr_ok(vals_size) || !ptr_ok(first_bad)) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  if (flags & ~(TKV_WAL_DECODE_KEY_VIEWS | TKV_WAL_DECODE_VAL_VIEWS))
+    return set_error(TKV_INVALID_ARGUMENT, "WAL decode: unknown flag bits");
+  if (n > 0xFFFFFFFFull) return set_error(TKV_INVALID_ARGUMENT, "WAL decode: more than 2^32 - 1 records");
+  if (n == 0) {
+    *keys_size = *vals_size = *first_bad = 0;
+    *done = true;
+    return TKV_OK;
+  }
+  if (ptr_ok(off64) == ptr_ok(off32)) return set_error(TKV_INVALID_ARGUMENT, "WAL decode: exactly one offset array");
+  if (ptr_ok(off32) && size > 0xFFFFFFFFull + 1ull)
+    return set_error(TKV_INVALID_ARGUMENT, "image larger than 4 GiB (u32 offsets)");
+  if (!ptr_ok(img)) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  return TKV_OK;
+}
+
+// Header fields of the record at h + off when it passes wal_entry::decode's structural checks
+// (wal.cpp:68, :83, :118-121; 64-bit arithmetic).
+bool decode_header(const std::uint8_t* h, std::uint64_t size, std::uint64_t off, std::uint32_t* kl, std::uint32_t* vl) {
+  if (off >= size || size - off < kWalMeta) return false;
+  std::uint32_t rlen;
+  std::memcpy(&rlen, h + off, 4);
+  std::memcpy(kl, h + off + kWalKeyLen, 4);
+  std::memcpy(vl, h + off + kWalValLen, 4);
+  return static_cast<std::uint64_t>(rlen) + kWalPayload <= size - off &&
+         static_cast<std::uint64_t>(*kl) + *vl + (kWalMeta - kWalPayload) <= rlen;
+}
+}  // namespace
+
+extern "C" {
+
+int tkv_wal_decode_device(const uint8_t* d_img, uint64_t size, const uint64_t* d_rec_off64, const uint32_t* d_rec_off32,
+                          uint64_t n, uint32_t flags, uint8_t* d_op, uint8_t* d_tomb, uint64_t* d_seq, uint64_t* d_key_off,
+                          uint32_t* d_key_len, uint64_t* d_val_off, uint32_t* d_val_len, uint8_t* d_keys, uint64_t keys_cap,
+                          uint8_t* d_vals, uint64_t vals_cap, uint64_t* keys_size, uint64_t* vals_size, uint64_t* first_bad,
+                          void* stream) {
+  bool done = false;
+  if (int rc = decode_check(d_img, size, d_rec_off64, d_rec_off32, n, flags, keys_size, vals_size, first_bad, &done)) return rc;
+  if (done) return TKV_OK;
+  *keys_size = *vals_size = 0;
+  *first_bad = n;
+  return wal_decode_device_impl(d_img, size, d_rec_off64, d_rec_off32, n, flags, d_op, d_tomb, d_seq, d_key_off, d_key_len,
+                                d_val_off, d_val_len, d_keys, keys_cap, d_vals, vals_cap, keys_size, vals_size, first_bad,
+                                static_cast<hipStream_t>(stream));
+}
+
+int tkv_wal_decode_host(const uint8_t* h_img, uint64_t size, const uint64_t* h_rec_off64, uint64_t n, uint32_t flags,
+                        uint8_t* h_op, uint8_t* h_tomb, uint64_t* h_seq, uint64_t* h_key_off, uint32_t* h_key_len,
+                        uint64_t* h_val_off, uint32_t* h_val_len, uint8_t* h_keys, uint64_t keys_cap, uint8_t* h_vals,
+                        uint64_t vals_cap, uint64_t* keys_size, uint64_t* vals_size, uint64_t* first_bad) {
+  bool done = false;
+  if (int rc = decode_check(h_img, size, h_rec_off64, nullptr, n, flags, keys_size, vals_size, first_bad, &done)) return rc;
+  if (done) return TKV_OK;
+  *keys_size = *vals_size = 0;
+  *first_bad = n;
+  const bool kviews = flags & TKV_WAL_DECODE_KEY_VIEWS, vviews = flags & TKV_WAL_DECODE_VAL_VIEWS;
+  // the header pass: lengths of the records that pass, the smallest failing index per thread's range
+  std::vector<std::uint64_t> ko(n + 1), vo(n + 1);
+  std::atomic<std::uint64_t> bad{n};
+  parallel_for(n, [&](std::uint64_t i) {
+    std::uint32_t kl = 0, vl = 0;
+    if (!decode_header(h_img, size, h_rec_off64[i], &kl, &vl)) {
+      kl = vl = 0;  // (never used as copy lengths)
+      std::uint64_t cur = bad.load(std::memory_order_relaxed);
+      while (i < cur && !bad.compare_exchange_weak(cur, i, std::memory_order_relaxed)) {
+      }
+    }
+    ko[i + 1] = kl;
+    vo[i + 1] = vl;
+  });
+  if (bad.load() < n) {
+    *first_bad = bad.load();
+    return set_error(TKV_CORRUPTED, "WAL decode: a record fails wal_entry::decode's structural checks");
+  }
+  ko[0] = vo[0] = 0;
+  for (std::uint64_t i = 0; i < n; ++i) {  // lengths to exclusive prefix sums, the totals last
+    ko[i + 1] += ko[i];
+    vo[i + 1] += vo[i];
+  }
+  *keys_size = ko[n];
+  *vals_size = vo[n];
+  const bool kcopy = !kviews && ko[n] != 0, vcopy = !vviews && vo[n] != 0;
+  if ((kcopy && ko[n] > keys_cap) || (vcopy && vo[n] > vals_cap))
+    return set_error(TKV_BUFFER_OVERFLOW, "WAL decode: an arena does not fit its cap");
+  if ((kcopy && !ptr_ok(h_keys)) || (vcopy && !ptr_ok(h_vals))) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  parallel_for(n, [&](std::uint64_t i) {
+    const std::uint64_t off = h_rec_off64[i];
+    const std::uint8_t* r = h_img + off;
+    const std::uint32_t kl = static_cast<std::uint32_t>(ko[i + 1] - ko[i]), vl = static_cast<std::uint32_t>(vo[i + 1] - vo[i]);
+    if (ptr_ok(h_op)) h_op[i] = r[kWalOp];
+    if (ptr_ok(h_tomb)) h_tomb[i] = r[kWalTomb];
+    if (ptr_ok(h_seq)) std::memcpy(&h_seq[i], r + kWalSeq, 8);
+    if (ptr_ok(h_key_len)) h_key_len[i] = kl;
+    if (ptr_ok(h_val_len)) h_val_len[i] = vl;
+    if (ptr_ok(h_key_off)) h_key_off[i] = kviews ? off + kWalMeta : ko[i];
+    if (ptr_ok(h_val_off)) h_val_off[i] = vviews ? off + kWalMeta + kl : vo[i];
+    if (kcopy && kl) std::memcpy(h_keys + ko[i], r + kWalMeta, kl);
+    if (vcopy && vl) std::memcpy(h_vals + vo[i], r + kWalMeta + kl, vl);
+  });
+  return TKV_OK;
 }
 
 

@@ -5,7 +5,7 @@
 // (little-endian, packed), record_len = 18 + key_len + val_len, crc32 = CRC-32 of bytes [8, 8 + record_len),
 // and the records lie back to back in batch order.
 //
-// enc_scan / enc_add: record sizes and their u64 exclusive prefix scan over n, kScanBlock records per
+// enc_scan / scan_level / scan_add (the levels: tkv_wal_copy.h): record sizes and their u64 exclusive prefix scan over n, kScanBlock records per
 // workgroup (DPP prefix per wave, wave totals through LDS), the block sums scanned by the next level,
 // up to kScanLevels levels. The host reads {total, overflow flag, long records} from a pinned block
 // and decides overflow / invalid before anything is written for the caller.
@@ -35,6 +35,7 @@
 #include "tkv_crc32_device.h"
 #include "tkv_device_util.h"
 #include "tkv_engine.h"
+#include "tkv_wal_copy.h"
 #include "tkv_wal_device.h"
 #include "tkv_wal_fold.h"
 #include "tkv_wal_layout.h"
@@ -48,11 +49,6 @@ constexpr std::uint32_t kEncOver = 288;       // window bytes past the tile
 constexpr std::uint32_t kEncWin = kEncPre + 16 + kEncTile + kEncOver;
 constexpr unsigned kEncWaves = 16;            // waves per workgroup: the 64 KiB tables + 16 windows of LDS
 constexpr unsigned kEncThreads = 64 * kEncWaves;
-constexpr std::uint32_t kShortSpan = 64;      // keys / values up to this long are copied by their record's lane
-constexpr unsigned kScanThreads = 256;
-constexpr unsigned kScanItems = 4;            // consecutive records per thread
-constexpr std::uint64_t kScanBlock = kScanThreads * kScanItems;  // records per workgroup of the size scan
-constexpr int kScanLevels = 4;                // kScanBlock^4 >= 2^32 records
 constexpr unsigned kEncHres = 4;              // words of the pinned result block
 enum : int { kCntFlag = 0, kCntLong, kCntCursor, kCntWords = 4 };
 // a folded record that starts in the tile's last byte ends, and fold_raw's frozen steps read, inside the window
@@ -90,61 +86,32 @@ struct EncArgs {
   const DeviceTables* tabs;
 };
 
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // ---- size scan --------------------------------------------------------------------------------------
 
 __device__ __forceinline__ std::uint64_t rec_len64(const EncArgs& a, std::uint64_t i) {
   return 18ull + a.key_len[i] + (a.val_len ? a.val_len[i] : 0u);
 }
 
-// Exclusive prefix within each block of kScanBlock entries, the block's sum to bsum[block]. LEVEL0: the
-// entries are the record sizes (written to a.off), the u32 overflow flag and the count of records the
-// emit pass does not stamp; else arr[0, m) in place.
-template <bool LEVEL0>
-__global__ __launch_bounds__(kScanThreads) void enc_scan(EncArgs a, std::uint64_t* arr, std::uint64_t m, std::uint64_t* bsum) {
+// Level 0 of the size scan (scan_items): the entries are the record sizes (their exclusive prefix within
+// the block to a.off), with the u32 overflow flag and the count of records the emit pass does not stamp.
+__global__ __launch_bounds__(kScanThreads) void enc_scan(EncArgs a, std::uint64_t* bsum) {
   const std::uint64_t i0 = blockIdx.x * kScanBlock + threadIdx.x * kScanItems;
   std::uint64_t v[kScanItems];
-  std::uint64_t s = 0;
   std::uint32_t nlong = 0, bad = 0;
 #pragma unroll
   for (unsigned k = 0; k < kScanItems; ++k) {
     const std::uint64_t i = i0 + k;
     v[k] = 0;
-    if (i < m) {
-      if constexpr (LEVEL0) {
-        const std::uint64_t rl = rec_len64(a, i);
-        v[k] = rl + kWalPayload;
-        bad |= rl > 0xFFFFFFFFull ? 1u : 0u;
-        nlong += (rl > kLaneFold || !a.fused) ? 1u : 0u;
-      } else {
-        v[k] = arr[i];
-      }
+    if (i < a.n) {
+      const std::uint64_t rl = rec_len64(a, i);
+      v[k] = rl + kWalPayload;
+      bad |= rl > 0xFFFFFFFFull ? 1u : 0u;
+      nlong += (rl > kLaneFold || !a.fused) ? 1u : 0u;
     }
-    s += v[k];
   }
-  std::uint64_t total;
-  std::uint64_t run = dev::block_prefix<std::uint64_t, kScanThreads>(s, &total);
-#pragma unroll
-  for (unsigned k = 0; k < kScanItems; ++k) {
-    const std::uint64_t i = i0 + k;
-    if (i < m) arr[i] = run;
-    run += v[k];
-  }
-  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-  if constexpr (LEVEL0) {
-    if (bad) atomicOr(&a.cnt[kCntFlag], 1ull);
-    if (nlong) atomicAdd(&a.cnt[kCntLong], static_cast<unsigned long long>(nlong));
-  }
-}
-
-__global__ __launch_bounds__(kScanThreads) void enc_add(std::uint64_t* arr, std::uint64_t m, const std::uint64_t* base) {
-  const std::uint64_t i = blockIdx.x * static_cast<std::uint64_t>(kScanThreads) + threadIdx.x;
-  if (i < m) arr[i] += base[i / kScanBlock];
+  scan_items(v, i0, a.n, a.off, bsum);
+  if (bad) atomicOr(&a.cnt[kCntFlag], 1ull);
+  if (nlong) atomicAdd(&a.cnt[kCntLong], static_cast<unsigned long long>(nlong));
 }
 
 __global__ void enc_publish(const std::uint64_t* top, const unsigned long long* cnt, std::uint64_t* h) {
@@ -190,162 +157,8 @@ __global__ __launch_bounds__(kScanThreads) void enc_stamp(EncArgs a, std::uint64
 
 // ---- emit -------------------------------------------------------------------------------------------
 
-// The aligned dword / granule at address p when it holds a byte of [s, e), else zero (no load leaves
-// the source span rounded out to its granules).
-// (Global address space: a generic load could alias the LDS window, and every load of a copy would then
-// wait for the window stores in front of it.)
-using GlobalU32 = const __attribute__((address_space(1))) std::uint32_t*;
-typedef std::uint32_t U32x4 __attribute__((ext_vector_type(4)));
-using GlobalU128 = const __attribute__((address_space(1))) U32x4*;
-__device__ __forceinline__ std::uint32_t ld4(std::uintptr_t p, std::uintptr_t s, std::uintptr_t e) {
-  return (p + 4u > s && p < e) ? *reinterpret_cast<GlobalU32>(p) : 0u;
-}
-__device__ __forceinline__ uint4 ld16(std::uintptr_t p, std::uintptr_t s, std::uintptr_t e) {
-  U32x4 v = {0u, 0u, 0u, 0u};
-  if (p + 16u > s && p < e) v = *reinterpret_cast<GlobalU128>(p);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-// The bytes of v (window bytes [q, q + 4)) that lie in [d, e).
-__device__ __forceinline__ void put4(std::uint8_t* win, std::uint32_t q, std::uint32_t v, std::uint32_t d, std::uint32_t e) {
-  if (q >= d && q + 4u <= e) {
-    *reinterpret_cast<std::uint32_t*>(win + q) = v;
-  } else {
-#pragma unroll
-    for (std::uint32_t b = 0; b < 4u; ++b)
-      if (q + b >= d && q + b < e) win[q + b] = static_cast<std::uint8_t>(v >> (8u * b));
-  }
-}
-
-// One lane's copy of len source bytes at src to window bytes [d, d + len) (nothing when on is false):
-// aligned source dwords, each window dword from two of them (v_alignbyte).
-struct LaneSpan {
-  std::uint32_t q, d, e, sh;      // next window dword, the span's window bytes, source misalignment
-  std::uintptr_t sa, s0, se;      // source address of window dword q rounded down, the source bytes
-};
-__device__ __forceinline__ LaneSpan lane_span(std::uint32_t d, std::uintptr_t src, std::uint32_t len, bool on) {
-  LaneSpan s{};
-  if (on) {
-    s.q = d & ~3u;
-    s.d = d;
-    s.e = d + len;
-    const std::uintptr_t sp = src - (d - s.q);  // source address of window byte q
-    s.sh = static_cast<std::uint32_t>(sp & 3u);
-    s.sa = sp & ~static_cast<std::uintptr_t>(3);
-    s.s0 = src;
-    s.se = src + len;
-  }
-  return s;
-}
-// Two such copies side by side (a record's key and value), four window dwords of each per step with the
-// step's ten loads issued together.
-__device__ __forceinline__ void lane_copy2(std::uint8_t* win, LaneSpan a, LaneSpan b) {
-  while (a.q < a.e || b.q < b.e) {
-    std::uint32_t wa[5], wb[5];
-#pragma unroll
-    for (std::uint32_t k = 0; k < 5u; ++k) {
-      wa[k] = ld4(a.sa + 4u * k, a.s0, a.se);
-      wb[k] = ld4(b.sa + 4u * k, b.s0, b.se);
-    }
-#pragma unroll
-    for (std::uint32_t k = 0; k < 4u; ++k) {
-      put4(win, a.q + 4u * k, __builtin_amdgcn_alignbyte(wa[k + 1u], wa[k], a.sh), a.d, a.e);
-      put4(win, b.q + 4u * k, __builtin_amdgcn_alignbyte(wb[k + 1u], wb[k], b.sh), b.d, b.e);
-    }
-    a.q += 16u;
-    a.sa += 16u;
-    b.q += 16u;
-    b.sa += 16u;
-  }
-}
-
-// The same by the whole wave (wave-uniform arguments), a 16-byte window granule per lane: the two
-// source granules that hold its bytes, shifted by the wave-uniform misalignment. A span covers at most
-// kWaveSteps steps of 64 granules (it lies in the window); their loads are issued together.
+// A span lies in the window: at most kWaveSteps steps of wave_copy.
 constexpr std::uint32_t kWaveSteps = (kEncWin + 1023u) / 1024u;
-__device__ __forceinline__ void wave_copy(std::uint8_t* win, std::uint32_t d, std::uintptr_t src, std::uint32_t len, std::uint32_t lane) {
-  const std::uint32_t e = d + len;
-  const std::uint32_t g0 = d & ~15u;
-  const std::uintptr_t sp0 = src - (d - g0);  // source address of window byte g0
-  const std::uint32_t r = static_cast<std::uint32_t>(sp0 & 15u);
-  const std::uint32_t k = r >> 2, sh = r & 3u;
-  const std::uintptr_t se = src + len;
-  uint4 As[kWaveSteps], Bs[kWaveSteps];
-#pragma unroll
-  for (std::uint32_t it = 0; it < kWaveSteps; ++it) {
-    const std::uint32_t g = g0 + 16u * lane + 1024u * it;
-    const std::uintptr_t sa = (sp0 + (g - g0)) & ~static_cast<std::uintptr_t>(15);
-    // (past the span's end sa >= se: nothing is loaded)
-    As[it] = ld16(sa, src, se);
-    Bs[it] = ld16(sa + 16u, src, se);
-  }
-#pragma unroll
-  for (std::uint32_t it = 0; it < kWaveSteps; ++it) {
-    const std::uint32_t g = g0 + 16u * lane + 1024u * it;
-    if (g >= e) break;
-    const uint4 A = As[it], B = Bs[it];
-    uint4 v;
-    switch (k) {
-      case 0:
-        v = make_uint4(__builtin_amdgcn_alignbyte(A.y, A.x, sh), __builtin_amdgcn_alignbyte(A.z, A.y, sh),
-                       __builtin_amdgcn_alignbyte(A.w, A.z, sh), __builtin_amdgcn_alignbyte(B.x, A.w, sh));
-        break;
-      case 1:
-        v = make_uint4(__builtin_amdgcn_alignbyte(A.z, A.y, sh), __builtin_amdgcn_alignbyte(A.w, A.z, sh),
-                       __builtin_amdgcn_alignbyte(B.x, A.w, sh), __builtin_amdgcn_alignbyte(B.y, B.x, sh));
-        break;
-      case 2:
-        v = make_uint4(__builtin_amdgcn_alignbyte(A.w, A.z, sh), __builtin_amdgcn_alignbyte(B.x, A.w, sh),
-                       __builtin_amdgcn_alignbyte(B.y, B.x, sh), __builtin_amdgcn_alignbyte(B.z, B.y, sh));
-        break;
-      default:
-        v = make_uint4(__builtin_amdgcn_alignbyte(B.x, A.w, sh), __builtin_amdgcn_alignbyte(B.y, B.x, sh),
-                       __builtin_amdgcn_alignbyte(B.z, B.y, sh), __builtin_amdgcn_alignbyte(B.w, B.z, sh));
-        break;
-    }
-    if (g >= d && g + 16u <= e) {
-      *reinterpret_cast<uint4*>(win + g) = v;
-    } else {
-      put4(win, g, v.x, d, e);
-      put4(win, g + 4u, v.y, d, e);
-      put4(win, g + 8u, v.z, d, e);
-      put4(win, g + 12u, v.w, d, e);
-    }
-  }
-}
-
-// A source span of len bytes at src that lies at image bytes [sx, sx + len), cut to the image bytes
-// [clo, chi) this wave lays out: its window offset (wb = window offset of image byte ts), source
-// address and length (0 when nothing is left).
-struct Span {
-  std::uint32_t d, len;
-  std::uintptr_t src;
-};
-__device__ __forceinline__ Span clip_span(std::uintptr_t src, std::uint64_t len, std::uint64_t sx, std::uint64_t clo,
-                                          std::uint64_t chi, std::uint64_t ts, std::uint32_t wb) {
-  const std::uint64_t c0 = sx > clo ? sx : clo;
-  const std::uint64_t c1 = sx + len < chi ? sx + len : chi;
-  Span s{0u, 0u, src};
-  if (c1 > c0) {
-    s.len = static_cast<std::uint32_t>(c1 - c0);
-    s.src = src + static_cast<std::uintptr_t>(c0 - sx);
-    s.d = wb + static_cast<std::uint32_t>(static_cast<std::int32_t>(static_cast<std::int64_t>(c0 - ts)));
-  }
-  return s;
-}
-
-// Long spans of the round's records, one after the other by the whole wave.
-__device__ __forceinline__ void wave_spans(std::uint8_t* win, const Span& s, std::uint32_t lane) {
-  unsigned long long m = __ballot(s.len > kShortSpan);
-  while (m) {
-    const std::uint32_t l = static_cast<std::uint32_t>(__ffsll(m)) - 1u;
-    m &= m - 1ull;
-    const std::uint32_t d = static_cast<std::uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(s.d), static_cast<int>(l)));
-    const std::uint32_t len = static_cast<std::uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(s.len), static_cast<int>(l)));
-    const std::uintptr_t src = static_cast<std::uintptr_t>(dev::readlane64(static_cast<std::uint64_t>(s.src), l));
-    wave_copy(win, d, src, len, lane);
-  }
-}
 
 // A record's inputs as the emit pass reads them, one record per lane.
 struct Rec {
@@ -420,8 +233,8 @@ __device__ __forceinline__ void emit_tile(const EncArgs& a, std::uint8_t* win, c
     }
     lane_copy2(win, lane_span(ks.d, ks.src, ks.len, ks.len != 0u && ks.len <= kShortSpan),
                lane_span(vs.d, vs.src, vs.len, vs.len != 0u && vs.len <= kShortSpan));
-    wave_spans(win, ks, lane);
-    wave_spans(win, vs, lane);
+    wave_spans<kWaveSteps>(win, ks, lane);
+    wave_spans<kWaveSteps>(win, vs, lane);
     wave_sync();
     // the lane fold (fold_raw plus the initial register's term), its CRC into the window's field
     const std::uint32_t L = fold ? rl : 0u;
@@ -436,20 +249,7 @@ __device__ __forceinline__ void emit_tile(const EncArgs& a, std::uint8_t* win, c
   // the tile out of the window: whole granules with 16-byte stores, the (at most two) granules shared
   // with a neighbour or with bytes outside the image bytewise
   const std::uint32_t len = static_cast<std::uint32_t>(te - ts);
-  const std::uint32_t ng = (o + len + 15u) >> 4;
-  std::uint8_t* const g0 = dst - o;
-  for (std::uint32_t j = lane; j < ng; j += 64u) {
-    const std::uint32_t lo = 16u * j, hi = lo + 16u;  // bytes from g0
-    const uint4 v = *reinterpret_cast<const uint4*>(win + kEncPre + lo);
-    if (lo >= o && hi <= o + len) {
-      *reinterpret_cast<uint4*>(g0 + lo) = v;
-    } else {
-      const std::uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (std::uint32_t b = 0; b < 16u; ++b)
-        if (lo + b >= o && lo + b < o + len) g0[lo + b] = static_cast<std::uint8_t>(w[b >> 2] >> (8u * (b & 3u)));
-    }
-  }
+  store_tile(win + kEncPre, dst, o, len, lane);
   wave_sync();
 }
 
@@ -525,29 +325,20 @@ int scratch(EncScratch** out) {
 }
 
 int encode_locked(EncScratch& s, EncArgs a, std::uint64_t cap, std::uint64_t* img_size, hipStream_t st) {
-  // entries of the scan levels: level k + 1 holds the block sums of level k, the last one a single sum
-  std::uint64_t m[kScanLevels + 1];
-  int levels = 0;
-  m[0] = a.n;
-  while (m[levels] > 1u || levels == 0) {
-    m[levels + 1] = (m[levels] + kScanBlock - 1u) / kScanBlock;
-    ++levels;
-  }
-  std::uint64_t nsum = 0;
-  for (int k = 1; k <= levels; ++k) nsum += m[k];
+  const ScanPlan plan(a.n);
+  const int levels = plan.levels;
+  const std::uint64_t* m = plan.m;
   if (int rc = grow(&s.off, &s.cap_off, a.n, 8)) return rc;
-  if (int rc = grow(&s.sums, &s.cap_sum, nsum, 8)) return rc;
+  if (int rc = grow(&s.sums, &s.cap_sum, plan.nsum, 8)) return rc;
   a.off = static_cast<std::uint64_t*>(s.off);
   a.cnt = s.cnt;
   std::uint64_t* lv[kScanLevels + 1];
-  lv[0] = a.off;
-  lv[1] = static_cast<std::uint64_t*>(s.sums);
-  for (int k = 2; k <= levels; ++k) lv[k] = lv[k - 1] + m[k - 1];
+  plan.place(a.off, static_cast<std::uint64_t*>(s.sums), lv);
   TKV_HIP_RC(hipMemsetAsync(s.cnt, 0, kCntWords * sizeof(unsigned long long), st));
   s.h_res[3] = 0;
-  hipLaunchKernelGGL(enc_scan<true>, dim3(static_cast<unsigned>(m[1])), dim3(kScanThreads), 0, st, a, lv[0], m[0], lv[1]);
+  hipLaunchKernelGGL(enc_scan, dim3(static_cast<unsigned>(m[1])), dim3(kScanThreads), 0, st, a, lv[1]);
   for (int k = 1; k < levels; ++k)
-    hipLaunchKernelGGL(enc_scan<false>, dim3(static_cast<unsigned>(m[k + 1])), dim3(kScanThreads), 0, st, a, lv[k], m[k], lv[k + 1]);
+    hipLaunchKernelGGL(scan_level, dim3(static_cast<unsigned>(m[k + 1])), dim3(kScanThreads), 0, st, lv[k], m[k], lv[k + 1]);
   hipLaunchKernelGGL(enc_publish, dim3(1), dim3(64), 0, st, lv[levels], s.cnt, s.d_hres);
   TKV_HIP_RC(hipGetLastError());
   TKV_HIP_RC(hipStreamSynchronize(st));
@@ -567,7 +358,7 @@ int encode_locked(EncScratch& s, EncArgs a, std::uint64_t cap, std::uint64_t* im
   a.l_idx = a.l_len + s.cap_long;
   a.l_crc = a.l_idx + s.cap_long;
   for (int k = levels - 2; k >= 1; --k)
-    hipLaunchKernelGGL(enc_add, dim3(blocks(m[k], kScanThreads)), dim3(kScanThreads), 0, st, lv[k], m[k], lv[k + 1]);
+    hipLaunchKernelGGL(scan_add, dim3(blocks(m[k], kScanThreads)), dim3(kScanThreads), 0, st, lv[k], m[k], lv[k + 1]);
   hipLaunchKernelGGL(enc_finish, dim3(blocks(a.n, kScanThreads)), dim3(kScanThreads), 0, st, a,
                      levels > 1 ? lv[1] : static_cast<const std::uint64_t*>(nullptr));
   const std::uint64_t want = (a.ntiles + kEncWaves - 1u) / kEncWaves;

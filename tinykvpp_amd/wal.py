@@ -13,8 +13,11 @@ stitching) and every record's CRC is checked in ONE batch (tkv_wal_verify; tkv_w
 an image already in HBM). Many records are stamped in one batch (tkv_wal_stamp) — the recovery loop
 of engine::create (engine.cpp:31-53) and group commit. A whole put batch held as keys, values and
 sequence numbers is encoded in one call (tkv_wal_encode: encode_batch; tkv_wal_encode_device for arenas
-already in HBM: encode_device), layout and CRCs included.
+already in HBM: encode_device), layout and CRCs included. The inverse takes the fields of a list of
+records out into that columnar form (tkv_wal_decode_device: decode_device; tkv_wal_decode_host:
+decode_batch), and recover_device / recover chain index and decode into what the recovery loop consumes.
 """
+import collections
 import ctypes
 import struct
 
@@ -278,6 +281,128 @@ def check_records_device(image, rec_offsets, max_payload=64, crc_out=None, first
         int(max_payload), ctypes.c_void_p(crc_out.data_ptr()), ctypes.c_void_p(first_bad.data_ptr()),
         _launch_stream(stream, image.device)))
     return first_bad, crc_out
+
+
+WalBatch = collections.namedtuple("WalBatch", "op tomb seq key_off key_len val_off val_len keys vals")
+WalBatch.__doc__ = """A decoded record list in the columnar form encode_device takes: per-record op, tomb, seq,
+key_off, key_len, val_off, val_len and the key / value arenas (for a views arena: the image itself)."""
+KEY_VIEWS, VAL_VIEWS = 1, 2  # TKV_WAL_DECODE_KEY_VIEWS / _VAL_VIEWS
+
+
+def decode_device(image, rec_off, size=None, key_views=False, val_views=False, stream=None):
+    """wal_entry::decode's fields (wal.cpp:98-127) for the records of a WAL image in a uint8 CUDA tensor
+    (first ``size`` bytes; default all) that start at ``rec_off``, an int64 or int32 (u32 offsets) CUDA
+    tensor such as index_device returns (tkv_wal_decode_device). Returns a WalBatch of CUDA tensors: op /
+    tomb uint8, seq / key_off / val_off int64, key_len / val_len int32 (u32 values) and the key / value
+    arenas, the keys (values) back to back in batch order, or the image itself with offsets into it with
+    ``key_views`` (``val_views``). The batch is what encode_device takes. No checksum is computed: the
+    offsets come from index_device or are checked by check_records_device. A record that fails
+    wal_entry::decode's structural checks raises ValueError naming its index. Synchronous on ``stream``."""
+    import torch
+    from ._lib import BUFFER_OVERFLOW
+    from .crc32 import _check_data, _check_vec, _launch_stream
+    if image.dtype != torch.uint8:
+        raise ValueError("image must be a uint8 tensor")
+    _check_data(image)
+    dev = image.device
+    size = image.numel() if size is None else int(size)
+    if size > image.numel():
+        raise ValueError("size exceeds the tensor")
+    if rec_off.dtype not in (torch.int64, torch.int32):
+        raise ValueError("rec_off must be an int64 or int32 (u32 offsets) tensor")
+    n = rec_off.numel()
+    _check_vec("rec_off", rec_off, rec_off.dtype, n, dev)
+    other = stream is not None and stream != torch.cuda.current_stream(dev)
+
+    def alloc(count, dtype):
+        t = torch.empty(count, dtype=dtype, device=dev)
+        if other:
+            t.record_stream(stream)
+        return t
+
+    def ptr(t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    flags = (KEY_VIEWS if key_views else 0) | (VAL_VIEWS if val_views else 0)
+    lib = load_library()
+    st = _launch_stream(stream, dev)
+    ks, vs, bad = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    off64, off32 = (ptr(rec_off), None) if rec_off.dtype == torch.int64 else (None, ptr(rec_off))
+
+    def call(cols, keys, vals):
+        return lib.tkv_wal_decode_device(ptr(image), size, off64, off32, n, flags, *[ptr(c) for c in cols], ptr(keys),
+                                         0 if keys is None else keys.numel(), ptr(vals),
+                                         0 if vals is None else vals.numel(), ctypes.byref(ks), ctypes.byref(vs),
+                                         ctypes.byref(bad), st)
+    rc = call([None] * 7, None, None)  # the sizing call
+    if rc == CORRUPTED:
+        raise ValueError(f"record {bad.value} of {n} fails wal_entry::decode's structural checks")
+    if rc not in (OK, BUFFER_OVERFLOW):
+        check(rc)
+    cols = [alloc(n, dt) for dt in (torch.uint8, torch.uint8, torch.int64, torch.int64, torch.int32, torch.int64,
+                                    torch.int32)]
+    keys = image if key_views else alloc(ks.value, torch.uint8)
+    vals = image if val_views else alloc(vs.value, torch.uint8)
+    rc = call(cols, None if key_views else keys, None if val_views else vals)
+    if rc == CORRUPTED:
+        raise ValueError(f"record {bad.value} of {n} fails wal_entry::decode's structural checks")
+    check(rc)
+    return WalBatch(*cols, keys, vals)
+
+
+def recover_device(image, size=None, key_views=False, val_views=False, stream=None):
+    """What engine::create's recovery loop (engine.cpp:31-53) consumes, for a WAL image in HBM:
+    index_device, then decode_device on the good records. Returns (status, WalBatch, stop_offset,
+    max_sequence); status, stop_offset and max_sequence are index_device's, the batch holds exactly the
+    good prefix."""
+    status, offs, stop, max_seq = index_device(image, size=size, stream=stream)
+    batch = decode_device(image, offs, size=size, key_views=key_views, val_views=val_views, stream=stream)
+    return status, batch, stop, max_seq
+
+
+def _host_image(wal_bytes):
+    if isinstance(wal_bytes, np.ndarray):
+        return np.ascontiguousarray(wal_bytes).reshape(-1).view(np.uint8)
+    return np.frombuffer(wal_bytes, np.uint8)
+
+
+def decode_batch(wal_bytes, rec_off, key_views=False, val_views=False):
+    """decode_device for an image held on the host (tkv_wal_decode_host: host threads, no GPU, no
+    checksum): ``rec_off`` a sequence of record start offsets such as index() returns. Returns a WalBatch
+    of numpy arrays (op / tomb uint8, seq / key_off / val_off uint64, key_len / val_len uint32, the
+    arenas uint8; a views arena is the image as a uint8 array)."""
+    from ._lib import BUFFER_OVERFLOW
+    buf = _host_image(wal_bytes)
+    off = np.ascontiguousarray(np.asarray(rec_off, dtype=np.uint64))
+    n = off.size
+    flags = (KEY_VIEWS if key_views else 0) | (VAL_VIEWS if val_views else 0)
+    ks, vs, bad = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+
+    def ptr(a):
+        return ctypes.c_void_p(a.ctypes.data) if a is not None and a.size else None
+
+    def call(cols, keys, vals):
+        return load_library().tkv_wal_decode_host(ptr(buf), buf.size, ptr(off), n, flags, *[ptr(c) for c in cols],
+                                                  ptr(keys), 0 if keys is None else keys.size, ptr(vals),
+                                                  0 if vals is None else vals.size, ctypes.byref(ks), ctypes.byref(vs),
+                                                  ctypes.byref(bad))
+    rc = call([None] * 7, None, None)  # the sizing call
+    if rc == CORRUPTED:
+        raise ValueError(f"record {bad.value} of {n} fails wal_entry::decode's structural checks")
+    if rc not in (OK, BUFFER_OVERFLOW):
+        check(rc)
+    cols = [np.empty(n, dt) for dt in (np.uint8, np.uint8, np.uint64, np.uint64, np.uint32, np.uint64, np.uint32)]
+    keys = buf if key_views else np.empty(ks.value, np.uint8)
+    vals = buf if val_views else np.empty(vs.value, np.uint8)
+    check(call(cols, None if key_views else keys, None if val_views else vals))
+    return WalBatch(*cols, keys, vals)
+
+
+def recover(wal_bytes, key_views=False, val_views=False):
+    """recover_device for a slurped WAL image on the host: index() (verify and list on the GPU), then
+    decode_batch (host threads) on the good records. Returns (status, WalBatch of numpy arrays,
+    stop_offset, max_sequence)."""
+    status, offs, stop, max_seq = index(wal_bytes)
+    return status, decode_batch(wal_bytes, offs, key_views=key_views, val_views=val_views), stop, max_seq
 
 
 def decode_fields(rec):
