@@ -8,9 +8,14 @@
 //    walk of tkv_wal_verify, /root/reference/src/engine/wal.cpp:63-87), on images whose pieces
 //    start inside records, cross giant records, and end at a corrupted header;
 //  * the multi-device split planner and its host combine step (tkv_debug_multi_plan,
-//    tkv_debug_multi_combine; the plan tkv_crc32_batch_host_multi runs on one thread per device).
-// Results are checked against a sequential walk and against the test oracle (oracle/crc32_oracle.c,
-// linked into this test only). Prints ALL PASSED.
+//    tkv_debug_multi_combine; the plan tkv_crc32_batch_host_multi runs on one thread per device);
+//  * the host WAL decode (tkv_wal_decode_host) on 40 000 records per caller: the header pass on host
+//    threads with its compare-exchange minimum for first_bad (one caller's image has two bad records
+//    in different threads' ranges), then the threaded scatter of the columns and the two arenas;
+//  * the host WAL encode layout (tkv_debug_wal_encode_layout) of the same batches, records written
+//    on host threads into one image.
+// Results are checked against a sequential walk, a sequential decode and layout written here, and the
+// test oracle (oracle/crc32_oracle.c, linked into this test only). Prints ALL PASSED.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -190,11 +195,170 @@ void check_multi_plans() {
   for (auto& x : th) x.join();
 }
 
+// ---- tkv_wal_decode_host / tkv_debug_wal_encode_layout (40 000 records: past parallel_for's 16 384) ----
+constexpr size_t kRecords = 40000;
+
+struct Image {
+  std::vector<uint8_t> bytes;
+  std::vector<uint64_t> off;
+};
+
+Image record_image(uint64_t seed) {
+  std::mt19937_64 rng(seed);
+  Image im;
+  for (size_t i = 0; i < kRecords; ++i) {
+    im.off.push_back(im.bytes.size());
+    put_record(im.bytes, rng() >> 2, static_cast<uint32_t>(rng() % 24), static_cast<uint32_t>(rng() % 65), rng);
+  }
+  return im;
+}
+
+struct Columns {
+  std::vector<uint8_t> op, tomb, keys, vals;
+  std::vector<uint64_t> seq, key_off, val_off;
+  std::vector<uint32_t> key_len, val_len;
+  uint64_t first_bad = 0;
+  bool operator==(const Columns& o) const {
+    return op == o.op && tomb == o.tomb && keys == o.keys && vals == o.vals && seq == o.seq && key_off == o.key_off &&
+           val_off == o.val_off && key_len == o.key_len && val_len == o.val_len && first_bad == o.first_bad;
+  }
+};
+
+// wal_entry::decode's structural checks and fields (wal.cpp:68, :83, :98-125), record after record. A bad
+// record: first_bad is its index and every column stays empty.
+Columns sequential_decode(const Image& im) {
+  Columns c;
+  const uint64_t size = im.bytes.size();
+  const uint8_t* w = im.bytes.data();
+  c.first_bad = im.off.size();
+  for (size_t i = 0; i < im.off.size(); ++i) {
+    const uint64_t p = im.off[i];
+    uint32_t rlen = 0, kl = 0, vl = 0;
+    bool ok = p < size && size - p >= 26;
+    if (ok) {
+      std::memcpy(&rlen, w + p, 4);
+      std::memcpy(&kl, w + p + 18, 4);
+      std::memcpy(&vl, w + p + 22, 4);
+      ok = uint64_t(rlen) + 8 <= size - p && 18 + uint64_t(kl) + vl <= rlen;
+    }
+    if (!ok) {
+      Columns bad;
+      bad.first_bad = i;
+      return bad;
+    }
+    uint64_t seq;
+    std::memcpy(&seq, w + p + 9, 8);
+    c.op.push_back(w[p + 8]);
+    c.tomb.push_back(w[p + 17]);
+    c.seq.push_back(seq);
+    c.key_off.push_back(c.keys.size());
+    c.val_off.push_back(c.vals.size());
+    c.key_len.push_back(kl);
+    c.val_len.push_back(vl);
+    c.keys.insert(c.keys.end(), w + p + 26, w + p + 26 + kl);
+    c.vals.insert(c.vals.end(), w + p + 26 + kl, w + p + 26 + kl + vl);
+  }
+  return c;
+}
+
+// The library's decode into 0xA5-filled outputs; on TKV_CORRUPTED every output must still be 0xA5 and is
+// returned empty, as sequential_decode returns it.
+Columns library_decode(const Image& im, uint64_t keys_cap, uint64_t vals_cap) {
+  const size_t n = im.off.size();
+  Columns c;
+  c.op.assign(n, 0xA5);
+  c.tomb.assign(n, 0xA5);
+  c.seq.assign(n, 0xA5A5A5A5A5A5A5A5ull);
+  c.key_off.assign(n, 0xA5A5A5A5A5A5A5A5ull);
+  c.val_off.assign(n, 0xA5A5A5A5A5A5A5A5ull);
+  c.key_len.assign(n, 0xA5A5A5A5u);
+  c.val_len.assign(n, 0xA5A5A5A5u);
+  c.keys.assign(keys_cap, 0xA5);
+  c.vals.assign(vals_cap, 0xA5);
+  const Columns filled = c;
+  uint64_t ks = 7, vs = 7;
+  const int rc = tkv_wal_decode_host(im.bytes.data(), im.bytes.size(), im.off.data(), n, 0, c.op.data(), c.tomb.data(),
+                                     c.seq.data(), c.key_off.data(), c.key_len.data(), c.val_off.data(), c.val_len.data(),
+                                     c.keys.data(), keys_cap, c.vals.data(), vals_cap, &ks, &vs, &c.first_bad);
+  if (rc == TKV_CORRUPTED) {
+    const uint64_t bad = c.first_bad;
+    c.first_bad = 0;
+    CHECK(c == filled);  // nothing written
+    CHECK(ks == 0 && vs == 0);
+    Columns none;
+    none.first_bad = bad;
+    return none;
+  }
+  CHECK(rc == TKV_OK);
+  CHECK(ks <= keys_cap && vs <= vals_cap);
+  if (ks <= keys_cap) c.keys.resize(ks);
+  if (vs <= vals_cap) c.vals.resize(vs);
+  return c;
+}
+
+std::vector<Image> decode_images() {
+  std::vector<Image> ims;
+  for (int t = 0; t < 4; ++t) ims.push_back(record_image(100 + t));
+  return ims;
+}
+
+void check_wal_decode_host() {
+  std::vector<Image> ims = decode_images();
+  // caller 1: two bad records in different threads' ranges (whatever the thread count: 30 000 lies past
+  // the middle, 12 000 in front of it); the smaller index is the answer
+  Image& bad = ims[1];
+  const uint32_t overrun = 0xFFFFFF00u, huge_key = 0xFFFFFFFFu;
+  std::memcpy(bad.bytes.data() + bad.off[30000], &overrun, 4);
+  std::memcpy(bad.bytes.data() + bad.off[12000] + 18, &huge_key, 4);
+  std::vector<Columns> want;
+  for (const auto& im : ims) want.push_back(sequential_decode(im));
+  CHECK(want[1].first_bad == 12000 && want[1].op.empty());
+  CHECK(want[0].first_bad == kRecords && want[0].op.size() == kRecords);
+  std::vector<std::thread> th;
+  for (int t = 0; t < 4; ++t)
+    th.emplace_back([&, t] {
+      for (int rep = 0; rep < 3; ++rep) {
+        const Columns got = library_decode(ims[t], 24 * kRecords, 65 * kRecords);
+        CHECK(got == want[t]);
+      }
+    });
+  for (auto& x : th) x.join();
+}
+
+void check_wal_encode_layout() {
+  const std::vector<Image> ims = decode_images();
+  std::vector<Columns> cols;
+  std::vector<std::vector<uint8_t>> want;  // the image with every CRC field zero (wal.cpp:28)
+  for (const auto& im : ims) {
+    cols.push_back(sequential_decode(im));
+    want.push_back(im.bytes);
+    for (const uint64_t p : im.off) std::memset(want.back().data() + p + 4, 0, 4);
+  }
+  std::vector<std::thread> th;
+  for (int t = 0; t < 4; ++t)
+    th.emplace_back([&, t] {
+      const Columns& c = cols[t];
+      for (int rep = 0; rep < 3; ++rep) {
+        std::vector<uint8_t> img(want[t].size() + 64, 0xA5);
+        uint64_t size = 0;
+        const size_t laid = tkv_debug_wal_encode_layout(c.keys.data(), c.key_off.data(), c.key_len.data(), c.vals.data(),
+                                                        c.val_off.data(), c.val_len.data(), c.op.data(), c.tomb.data(),
+                                                        c.seq.data(), 0, kRecords, img.data(), want[t].size(), &size);
+        CHECK(laid == kRecords && size == want[t].size());
+        CHECK(std::memcmp(img.data(), want[t].data(), want[t].size()) == 0);
+        for (size_t i = want[t].size(); i < img.size(); ++i) CHECK(img[i] == 0xA5);
+      }
+    });
+  for (auto& x : th) x.join();
+}
+
 }  // namespace
 
 int main() {
   check_wal_chains();
   check_multi_plans();
+  check_wal_decode_host();
+  check_wal_encode_layout();
   if (g_fail) {
     std::printf("%d FAILED\n", g_fail);
     return 1;

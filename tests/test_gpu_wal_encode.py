@@ -266,3 +266,16 @@ def test_python_host_path(gpu, lib, oracle):
     assert image == want
     exp, exp_off, _ = expected(list_batch(keys, vals, first_seq=77), oracle)
     assert image == exp.tobytes() and np.array_equal(offs, exp_off)
+
+
+def test_host_entry_on_host_threads(gpu, lib, oracle):
+    """tkv_wal_encode at 50 000 records: the layout and the CRC fields are written on host threads
+    (n >= 1 << 14); image, rec_off and crc against the numpy encode."""
+    rng = np.random.default_rng(908)
+    b = small_batch(rng, 50_000)
+    want, offs, crc = expected(b, oracle)
+    rc, size, img, guard, goff, gcrc = encode_host(lib, b, align=7)
+    assert rc == OK and size == want.size and guard
+    bad = np.flatnonzero(img != want)
+    assert bad.size == 0, f"image differs at {bad[:8]} (first record {np.searchsorted(offs, bad[0], 'right') - 1})"
+    assert np.array_equal(goff, offs) and np.array_equal(gcrc, crc)

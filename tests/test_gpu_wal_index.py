@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import tinykvpp_amd as tk
+from wal_fuzz_util import decode  # the sequential decode every case is compared with
 
 pytestmark = pytest.mark.gpu
 
@@ -94,38 +95,6 @@ def join(recs):
 
 # ---- the expected index ---------------------------------------------------------------------------
 
-def decode(oracle, img, size):
-    """wal_entry::decode record after record (engine.cpp:31-53): (status, n_good, stop_offset), the
-    good records' starts (uint64) and their largest sequence_ (0 for none)."""
-    img = np.ascontiguousarray(img[:size])
-    b = img.tobytes()
-    starts, p, broke = [], 0, False
-    while p < size:
-        if size - p < 26:
-            broke = True
-            break
-        rlen = int.from_bytes(b[p:p + 4], "little")
-        if rlen + 8 > size - p:
-            broke = True
-            break
-        starts.append(p)
-        p += 8 + rlen
-    r = np.array(starts, np.uint64)
-    status, n_good, stop = ("corrupted" if broke else "ok"), len(starts), p
-    if starts:
-        at = r.astype(np.int64)
-        field = lambda o, w, t: img[at[:, None] + o + np.arange(w)].copy().view(t).reshape(-1)  # noqa: E731
-        rl, stored = field(0, 4, "<u4"), field(4, 4, "<u4")
-        kl, vl = field(18, 4, "<u4").astype(np.uint64), field(22, 4, "<u4").astype(np.uint64)
-        got = oracle.batch(img, r + 8, rl)
-        bad = np.flatnonzero((got != stored) | (26 + kl + vl > 8 + rl.astype(np.uint64)))
-        if bad.size:
-            status, n_good, stop = "corrupted", int(bad[0]), int(r[bad[0]])
-        seq = field(9, 8, "<u8")[:n_good]
-    mseq = int(seq.max()) if starts and n_good else 0
-    return (status, n_good, stop), r[:n_good], mseq
-
-
 def wal_last():
     out = (U64 * 4)()
     tk.load_library().tkv_debug_wal_last(out)
@@ -139,9 +108,10 @@ def to_device(img, size, shift=0):
     return d[shift:]
 
 
-def index_raw(view, size, cap, use64=True, use32=True):
+def index_raw(view, size, cap, use64=True, use32=True, tensors=False):
     """tkv_wal_index_device on a device image with sentinel-filled offsets buffers of cap + PAD
-    entries: ((status, n_good, stop), offsets64, offsets32 (numpy, whole buffers), max_sequence)."""
+    entries: ((status, n_good, stop), offsets64, offsets32 (numpy, whole buffers), max_sequence); with
+    `tensors` also the two device buffers themselves, for a next stage that reads them in place."""
     o64 = torch.full((cap + PAD,), SENT64, dtype=torch.int64, device="cuda")
     o32 = torch.full((cap + PAD,), SENT32, dtype=torch.int32, device="cuda")
     good, stop, seq = U64(0), U64(0), U64(0)
@@ -151,7 +121,8 @@ def index_raw(view, size, cap, use64=True, use32=True):
         VP(torch.cuda.current_stream().cuda_stream))
     assert rc in (0, 4), (rc, tk.load_library().tkv_last_error())
     torch.cuda.synchronize()
-    return (("ok" if rc == 0 else "corrupted"), good.value, stop.value), o64.cpu().numpy(), o32.cpu().numpy(), seq.value
+    res = (("ok" if rc == 0 else "corrupted"), good.value, stop.value), o64.cpu().numpy(), o32.cpu().numpy(), seq.value
+    return res + ((o64, o32),) if tensors else res
 
 
 def check(oracle, img, size, shift=0, cap=None):

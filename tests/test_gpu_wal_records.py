@@ -15,40 +15,13 @@ import torch
 import tinykvpp_amd as tk
 from conftest import golden
 from test_gpu_wal_device import make_wal
+from wal_fuzz_util import records_expected as expected  # per record: (computed CRC or 0, ok)
 
 pytestmark = pytest.mark.gpu
 
 
 def u32at(img, p):
     return int.from_bytes(img[p:p + 4].tobytes(), "little")
-
-
-def expected(oracle, img, size, offs):
-    """Per record: (computed CRC or 0 when its length check fails, ok)."""
-    offs = np.asarray(offs, np.int64)
-    n = offs.size
-    crc = np.zeros(n, np.uint32)
-    ok = np.zeros(n, bool)
-    left = np.where(offs < size, size - offs, 0)
-    hdr = left >= 26
-    idx = np.flatnonzero(hdr)
-    rlen = np.zeros(n, np.int64)
-    if idx.size:
-        o = offs[idx]
-        b = img[(o[:, None] + np.arange(26)).astype(np.int64)]
-        rl = b[:, 0:4].copy().view("<u4").reshape(-1).astype(np.int64)
-        rlen[idx] = rl
-    len_ok = hdr & (rlen + 8 <= left)
-    li = np.flatnonzero(len_ok)
-    if li.size:
-        o = offs[li]
-        crc[li] = oracle.batch(img, (o + 8).astype(np.uint64), rlen[li].astype(np.uint32))
-        b = img[(o[:, None] + np.arange(26)).astype(np.int64)]
-        stored = b[:, 4:8].copy().view("<u4").reshape(-1)
-        klen = b[:, 18:22].copy().view("<u4").reshape(-1).astype(np.int64)
-        vlen = b[:, 22:26].copy().view("<u4").reshape(-1).astype(np.int64)
-        ok[li] = (crc[li] == stored) & (18 + klen + vlen <= rlen[li])
-    return crc, ok
 
 
 def run(img, offs, max_payload, shift=0, gpu="cuda:0"):

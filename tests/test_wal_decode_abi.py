@@ -1,7 +1,8 @@
 """tkv_wal_decode_host / tkv_wal_decode_device: what can be checked without a GPU. The symbols are
 exported and declared, the host decode equals a numpy restatement of wal.cpp:98-125 on the golden
 records and on random batches at odd arena alignments, its outputs feed the encode layout back to the
-same image, and sizing, overflow, corruption and argument errors leave every output untouched."""
+same image, and sizing, overflow, corruption and argument errors leave every output untouched. The same
+on 50 000 records, where the header pass, the first_bad minimum and the scatter run on host threads."""
 import ctypes
 import os
 import re
@@ -231,3 +232,95 @@ def test_python_host_entry(lib, random_case):
     bimg, size, boffs = corrupt("record_len", img, offs, 33)
     with pytest.raises(ValueError, match="record 33"):
         tk.wal.decode_batch(bimg[:size], boffs)
+
+
+# ---- the threaded branch of the host call (parallel_for goes to host threads at n >= 1 << 14) ---------------
+
+THREADED_N = 50_000
+
+
+def host_threads():
+    """How many threads the library's host loops use: the CPUs this process may run on, capped by
+    OMP_NUM_THREADS and 16 (tkv_formats.cpp host_threads, restated)."""
+    n = min(16, len(os.sched_getaffinity(0)))
+    v = os.environ.get("OMP_NUM_THREADS", "")
+    if v.strip().lstrip("+").isdigit() and int(v) > 0:
+        n = min(n, int(v))
+    return max(1, n)
+
+
+@pytest.fixture(scope="module")
+def threaded_case():
+    """50 000 records: every per-thread range n t / nt .. n (t + 1) / nt holds thousands of them."""
+    if host_threads() < 2:
+        pytest.skip("this process may use one CPU: the host loops stay serial")
+    rng = np.random.default_rng(1210)
+    b = make_batch(rng, rng.integers(0, 24, THREADED_N), rng.integers(0, 65, THREADED_N))
+    b["tomb"] = rng.integers(0, 2, THREADED_N).astype(np.uint8)
+    img, offs, _ = encoded(b)
+    return b, img, offs
+
+
+@pytest.mark.parametrize("align", (0, 11))
+def test_threaded_full_decode(lib, threaded_case, align):
+    b, img, offs = threaded_case
+    for flags in FLAGS:
+        out, want = check_host(lib, img, offs, flags, kalign=align, valign=(align + 6) % 16)
+        assert np.array_equal(want["key_len"], b["key_len"]) and np.array_equal(want["seq"], b["seq"])
+
+
+def test_threaded_permutation_with_a_duplicate(lib, threaded_case):
+    _, img, offs = threaded_case
+    p = np.random.default_rng(1211).permutation(offs.size)
+    p[40_017] = p[3]
+    for flags in (0, KEY_VIEWS | VAL_VIEWS):
+        check_host(lib, img, offs[p], flags, kalign=9, valign=2)
+
+
+def test_threaded_bad_records_in_three_ranges(lib, threaded_case):
+    """Three bad records in three threads' ranges, the smallest not in the first range: the smallest
+    index comes back (the compare-exchange minimum across threads) and nothing is written."""
+    _, img, offs = threaded_case
+    n, nt = offs.size, host_threads()
+    bads = (45_000, 20_000, 33_000) if nt >= 3 else (45_000, 26_000, 33_000)
+    assert min(bads) >= n // nt and (nt < 3 or len({b * nt // n for b in bads}) == 3)
+    bimg, size, boffs = corrupt("record_len", img, offs, bads[0])
+    bimg, size, boffs = corrupt("key_len", bimg, boffs, bads[2])
+    bimg, size, boffs = corrupt("short", bimg, boffs, bads[1])
+    assert first_bad(bimg, boffs, size) == min(bads)
+    for flags in (0, KEY_VIEWS | VAL_VIEWS):
+        out = HostOut(n, 1 << 21, 1 << 22, 5, 5)
+        assert decode_host(lib, bimg, boffs, flags, out, size=size) == (CORRUPTED, 0, 0, min(bads))
+        assert out.untouched()
+
+
+@pytest.mark.parametrize("where", ("first", "last"))
+def test_threaded_only_bad_record_at_an_end(lib, threaded_case, where):
+    _, img, offs = threaded_case
+    n = offs.size
+    i = 0 if where == "first" else n - 1
+    bimg, size, boffs = corrupt("record_len", img, offs, i)
+    assert first_bad(bimg, boffs, size) == i
+    out = HostOut(n, 1 << 21, 1 << 22, 3, 8)
+    assert decode_host(lib, bimg, boffs, 0, out, size=size) == (CORRUPTED, 0, 0, i) and out.untouched()
+
+
+def test_serial_and_threaded_side_by_side(lib, threaded_case):
+    """n = 16 383 (one thread) and n = 16 384 (host threads) of the same records."""
+    _, img, offs = threaded_case
+    for n in ((1 << 14) - 1, 1 << 14):
+        for flags in FLAGS:
+            check_host(lib, img, offs[:n], flags, kalign=7, valign=1)
+
+
+def test_threaded_with_three_threads(lib, threaded_case, monkeypatch):
+    """An odd thread count: uneven ranges. OMP_NUM_THREADS is only ever lowered."""
+    _, img, offs = threaded_case
+    if host_threads() > 3:
+        monkeypatch.setenv("OMP_NUM_THREADS", "3")
+    for flags in FLAGS:
+        check_host(lib, img, offs, flags, kalign=13, valign=4)
+    bimg, size, boffs = corrupt("record_len", img, offs, 40_000)
+    bimg, size, boffs = corrupt("short", bimg, boffs, 17_000)
+    out = HostOut(offs.size, 1 << 21, 1 << 22)
+    assert decode_host(lib, bimg, boffs, 0, out, size=size) == (CORRUPTED, 0, 0, 17_000) and out.untouched()

@@ -1,6 +1,7 @@
 """tkv_wal_encode / tkv_wal_encode_device: what can be checked without a GPU. The symbols are exported
 and declared, the host layout step (CRC fields zero) equals a numpy restatement of wal.cpp:19-61 and the
-golden records, and sizing, overflow and argument errors are decided before any device work."""
+golden records (also at 50 000 records, laid out on host threads), and sizing, overflow and argument
+errors are decided before any device work."""
 import ctypes
 import os
 import re
@@ -125,3 +126,20 @@ def test_geometry(lib):
     assert fold_max >= 240
     assert per_wg >= 64 and levels >= 1 and per_wg ** levels >= 1 << 32
     assert lib.tkv_debug_set_wal_encode_fused(1) == 1  # the default
+
+
+def test_layout_on_host_threads(lib):
+    """The layout at 50 000 records and on either side of 16 384 (parallel_for goes to host threads at
+    n >= 1 << 14; with one usable CPU both branches are the serial one): explicit columns, and all the
+    defaults (no values, op / tombstone 0, seq = first_seq + i)."""
+    rng = np.random.default_rng(85)
+    n = 50_000
+    b = make_batch(rng, rng.integers(0, 24, n), rng.integers(0, 65, n))
+    for m in (n, (1 << 14) - 1, 1 << 14):
+        part = dict(b, n=m, **{k: b[k][:m] for k in ("key_off", "key_len", "val_off", "val_len", "op", "tomb", "seq")})
+        for d in (part, dict(part, val_len=None, op=None, tomb=None, seq=None, first_seq=1 << 40)):
+            want = expected(d)[0]
+            got, size, img = layout(lib, d)
+            assert (got, size) == (m, want.size)
+            bad = np.flatnonzero(img != want)
+            assert bad.size == 0, f"n = {m}: the image differs in {bad.size} bytes, first at {bad[0]}"

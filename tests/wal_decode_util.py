@@ -218,16 +218,19 @@ def decode_device(lib, image, doffs, flags, out, size=None, stream=None):
     return rc, ks.value, vs.value, fb.value
 
 
-def check_device(lib, dev, image, img, offs, flags, kalign=0, valign=0, u32=False, stream=None, want=None):
+def check_device(lib, dev, image, img, offs, flags, kalign=0, valign=0, u32=False, stream=None, want=None, doffs=None):
     """A full decode on the device of image (= img on the host) against expected(), every column and
-    arena byte and the sentinels; returns (out, want)."""
+    arena byte and the sentinels; returns (out, want). doffs: a device list that holds offs already
+    (int64 or int32), read in place instead of an upload of offs."""
     want = expected(img, offs, flags) if want is None else want
     kcap = None if flags & KEY_VIEWS else want["keys_size"]
     vcap = None if flags & VAL_VIEWS else want["vals_size"]
     out = DevOut(dev, len(offs), kcap, vcap, kalign, valign)
     if kcap is not None:
         assert (out.kbuf.data_ptr() + out.kstart) % 16 == kalign % 16
-    rc, ks, vs, fb = decode_device(lib, image, dev_offsets(dev, offs, u32), flags, out, stream=stream)
+    doffs = dev_offsets(dev, offs, u32) if doffs is None else doffs
+    assert doffs.numel() == len(offs)
+    rc, ks, vs, fb = decode_device(lib, image, doffs, flags, out, stream=stream)
     assert (rc, ks, vs, fb) == (0, want["keys_size"], want["vals_size"], len(offs)), (rc, ks, vs, fb)
     assert out.guards_ok(ks, vs), "bytes outside a destination were written"
     compare(out.cols(), None if kcap is None else out.arena("keys", ks).cpu().numpy(),
