@@ -176,6 +176,66 @@ int tkv_wal_index_device(const uint8_t *d_wal, uint64_t size, uint64_t *d_off64,
 int tkv_wal_index(const uint8_t *h_wal, uint64_t size, uint64_t *h_off64, uint64_t cap, uint64_t *n_good,
                   uint64_t *stop_offset, uint64_t *max_sequence);
 
+/* ---- WAL salvage: resynchronise past corrupted records ------------------------- */
+
+/* Everything above stops at the first bad record, as wal_entry::decode and engine::create do. The calls
+ * below go on behind it. valid(p), for an image [0, size), holds when (all arithmetic 64-bit)
+ *   1. size - p >= 26;
+ *   2. rl + 8 <= size - p, rl the u32 LE at p;
+ *   3. 18 + kl + vl <= rl, kl and vl the u32 LE at p + 18 and p + 22;
+ *   4. the finalized CRC-32 of bytes [p + 8, p + 8 + rl) equals the u32 LE at p + 4
+ * - the checks of tkv_wal_check_records_device. The salvage of an image is the sequential program
+ *     p = 0; while p < size: if valid(p): emit record p, p += 8 + rl(p); else: p is skipped, p += 1
+ * and a gap [a, b) is a maximal run of skipped bytes (b == size: a tail gap). Two consequences of the
+ * definition: a candidate that passes by CRC collision (2^-32 per structurally plausible candidate) is
+ * accepted, and so are valid records nested inside a corrupted record's value (their bytes are in a
+ * skipped range). Cost: every byte offset of a damaged range is tested (checks 1-3), and each survivor
+ * costs the CRC of its record_len bytes; a crafted image whose damaged range is dense with plausible
+ * headers and long record_len values costs candidates x payload bytes of CRC work, which a sequential
+ * salvage pays as well. */
+
+/* Smallest p >= from with valid(p). TKV_OK and *found = p; TKV_NOT_FOUND and *found = size when there
+ * is none (from == size included). from > size, NULL d_wal with size > 0, NULL found:
+ * TKV_INVALID_ARGUMENT, decided before any device work. Synchronous on `stream`. No byte outside the
+ * 16-byte granules of [d_wal, d_wal + size) is read, whatever the header fields say. No CRC on the CPU;
+ * no usable GPU: TKV_IO_ERROR. The search runs in spans of start offsets from `from` (64 KiB first,
+ * four times longer each, 16 MiB at most); structurally plausible candidates are checked in offset
+ * order in batches of bounded payload bytes, and the search ends with the batch that holds the answer. */
+int tkv_wal_resync_device(const uint8_t *d_wal, uint64_t size, uint64_t from, uint64_t *found, void *stream);
+
+/* The salvage program above, as a loop of tkv_wal_index_device on the sub-image [p, size) and
+ * tkv_wal_resync_device from its stop offset + 1.
+ * d_off64 (device, cap entries, nullable when cap == 0): start offsets, absolute in the image, of the
+ *   first min(*n_records, cap) salvaged records in increasing order; *n_records is the full count.
+ * h_gaps (host, 2 * gap_cap u64, nullable when gap_cap == 0): {start, end} of the first
+ *   min(*n_gaps, gap_cap) gaps; *n_gaps is the full count.
+ * max_gaps: at most this many resynchronisations. On meeting invalid position g with max_gaps gaps
+ *   already closed the call stops: *stop_offset = g, and the records and gaps listed are those before g.
+ *   Otherwise *stop_offset = size. With max_gaps == 0 status, *n_records, *stop_offset, *max_sequence
+ *   and the offsets are exactly tkv_wal_index_device's on the same image.
+ * *max_sequence: largest sequence_ over the salvaged records, 0 for none.
+ * *bytes_skipped: sum of the closed gaps' lengths, listed or not.
+ * TKV_OK iff *n_gaps == 0 and *stop_offset == size (then identical to a clean index); else
+ * TKV_CORRUPTED with every output valid. Argument errors as tkv_wal_index_device (and gap_cap > 0 with
+ * NULL h_gaps), decided first. When the index of a sub-image hands over to the exact host walk (its
+ * fix-up round budget), that walk's records are taken and the salvage stops resynchronising there:
+ * *stop_offset is that stop, the status TKV_CORRUPTED. Synchronous on `stream`. */
+int tkv_wal_salvage_device(const uint8_t *d_wal, uint64_t size, uint64_t *d_off64, uint64_t cap,
+                           uint64_t *h_gaps, uint64_t gap_cap, uint64_t max_gaps, uint64_t *n_records,
+                           uint64_t *n_gaps, uint64_t *stop_offset, uint64_t *bytes_skipped,
+                           uint64_t *max_sequence, void *stream);
+
+/* Host image (pageable or pinned): copied to the device the way tkv_wal_index copies it, salvaged
+ * there, the offsets copied back to h_off64 (cap entries; may be NULL when cap is 0). The device copies
+ * of the image and of the offsets are kept per device between calls, up to 256 MiB each, and the work
+ * runs on a stream of the library's own; calls on one device take turns. When the device
+ * cannot hold the image or its offsets, the result is tkv_wal_index's (its exact host walk) with
+ * *stop_offset at its stop, *n_gaps = 0, and nothing is resynchronised; likewise behind a sub-image
+ * whose index used up its round budget (above). */
+int tkv_wal_salvage(const uint8_t *h_wal, uint64_t size, uint64_t *h_off64, uint64_t cap, uint64_t *h_gaps,
+                    uint64_t gap_cap, uint64_t max_gaps, uint64_t *n_records, uint64_t *n_gaps,
+                    uint64_t *stop_offset, uint64_t *bytes_skipped, uint64_t *max_sequence);
+
 /* Stamp n records in place (host memory): for record i at h_buf + h_offsets[i] of total size
  * h_sizes[i] (>= 8), write crc32 of bytes [8, size) LE at offset 4 (wal.cpp:54-58). */
 int tkv_wal_stamp(uint8_t *h_buf, const uint64_t *h_offsets, const uint32_t *h_sizes, uint64_t n);
@@ -475,7 +535,17 @@ void tkv_debug_wal_decode_geometry(uint64_t out[4]);
  * out[1] = emit waves for the value arena (0 for a views or empty arena), out[2] = key bytes, out[3] =
  * value bytes (all 0 when it wrote nothing). */
 void tkv_debug_wal_decode_last(uint64_t out[4]);
-
+/* Geometry of tkv_wal_resync_device's search: out[0] = start offsets one wave tests per window, out[1] =
+ * start offsets of a search's first span, out[2] = of its largest (spans grow fourfold in between),
+ * out[3] = the one fixed-size hand-over of the search: the long candidates (record_len above 64 KiB) in
+ * front of a batch's first valid short one that are folded one by one; a batch with more of them, which
+ * one window can hold, takes the overflow route, a second run of the batch engine over its list. Short
+ * candidates have no such limit: the survivor masks hold every density. */
+void tkv_debug_wal_salvage_geometry(uint64_t out[4]);
+/* What the calling thread's last tkv_wal_resync_device or tkv_wal_salvage[_device] did: out[0] =
+ * resynchronisations, out[1] = search spans launched, out[2] = start offsets tested, out[3] = candidates
+ * whose CRC was computed, out[4] = payload bytes folded for them, out[5] = index calls. */
+void tkv_debug_wal_salvage_last(uint64_t out[6]);
 
 #ifdef __cplusplus
 }

@@ -24,4 +24,4 @@ from .crc32 import (  # noqa: F401
     set_device,
 )
 from . import sst, wal  # noqa: F401
-from .wal import WalBatch  # noqa: F401
+from .wal import WalBatch, resync_device, salvage, salvage_device  # noqa: F401

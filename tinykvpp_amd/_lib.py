@@ -54,6 +54,11 @@ SIGNATURES = {
                                     ctypes.POINTER(_u64), _vp]),
     "tkv_wal_index": (_int, [_u8p, _u64, _vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                              ctypes.POINTER(_u64)]),
+    "tkv_wal_resync_device": (_int, [_u8p, _u64, _u64, ctypes.POINTER(_u64), _vp]),
+    "tkv_wal_salvage_device": (_int, [_u8p, _u64, _vp, _u64, _vp, _u64, _u64] + [ctypes.POINTER(_u64)] * 5 + [_vp]),
+    "tkv_wal_salvage": (_int, [_u8p, _u64, _vp, _u64, _vp, _u64, _u64] + [ctypes.POINTER(_u64)] * 5),
+    "tkv_debug_wal_salvage_geometry": (None, [_vp]),
+    "tkv_debug_wal_salvage_last": (None, [_vp]),
     "tkv_wal_stamp": (_int, [_u8p, _vp, _vp, _u64]),
     "tkv_wal_encode_device": (_int, [_u8p, _vp, _vp, _u8p, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u8p, _u64, _vp, _vp,
                                      ctypes.POINTER(_u64), _vp]),
@@ -113,7 +118,8 @@ OPTIONAL = {"tkv_build_id", "tkv_wal_index_device", "tkv_wal_index", "tkv_debug_
             "tkv_debug_set_packed_fold", "tkv_wal_encode_device", "tkv_wal_encode", "tkv_debug_wal_encode_layout",
             "tkv_debug_wal_encode_geometry", "tkv_debug_wal_encode_last", "tkv_debug_set_wal_encode_fused",
             "tkv_wal_decode_device", "tkv_wal_decode_host", "tkv_debug_wal_decode_geometry",
-            "tkv_debug_wal_decode_last"}
+            "tkv_debug_wal_decode_last", "tkv_wal_resync_device", "tkv_wal_salvage_device", "tkv_wal_salvage",
+            "tkv_debug_wal_salvage_geometry", "tkv_debug_wal_salvage_last"}
 
 _lib = None
 

@@ -10,10 +10,12 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <thread>
 #include <vector>
 
 #include "tkv_crc32.h"
+#include "tkv_device_util.h"
 #include "tkv_engine.h"
 #include "tkv_wal_device.h"
 #include "tkv_wal_layout.h"
@@ -212,6 +214,98 @@ std::uint64_t max_sequence_of(const std::uint8_t* w, const std::vector<std::uint
   return mx;
 }
 
+// tkv_wal_index_device behind its argument checks: the device index, or the exact host walk when the
+// device hands over (*walked, nullable, says which).
+int index_device_any(const uint8_t* d_wal, uint64_t size, uint64_t* d_off64, uint32_t* d_off32, uint64_t cap,
+                     uint64_t* n_good, uint64_t* stop_offset, uint64_t* max_sequence, hipStream_t st, bool* walked) {
+  *n_good = *stop_offset = *max_sequence = 0;
+  if (size == 0) return TKV_OK;
+  bool host_walk = false;
+  if (walked) *walked = false;
+  const int rc = wal_index_device_impl(d_wal, size, d_off64, d_off32, cap, n_good, stop_offset, max_sequence,
+                                       st, &host_walk);
+  if (!host_walk) return rc;
+  if (walked) *walked = true;
+  // the verify's exact fallback (tkv_wal_verify_device): its walk's positions go to the caller's arrays,
+  // the copies on the caller's stream
+  std::vector<std::uint8_t> h(size);
+  if (hipMemcpyAsync(h.data(), d_wal, size, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return set_error(TKV_IO_ERROR, "WAL image copy to host failed");
+  std::vector<std::uint64_t> pos;
+  const int rw = wal_verify_host_walk(h.data(), size, n_good, stop_offset, &pos);
+  if (rw != TKV_OK && rw != TKV_CORRUPTED) return rw;
+  *max_sequence = max_sequence_of(h.data(), pos);
+  const std::size_t n = static_cast<std::size_t>(std::min<std::uint64_t>(pos.size(), cap));
+  std::vector<std::uint32_t> p32;
+  if (n && ptr_ok(d_off32)) p32.assign(pos.begin(), pos.begin() + static_cast<std::ptrdiff_t>(n));
+  bool ok = true;
+  if (n && ptr_ok(d_off64)) ok = hipMemcpyAsync(d_off64, pos.data(), n * 8, hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok && n && ptr_ok(d_off32)) ok = hipMemcpyAsync(d_off32, p32.data(), n * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+  if (hipStreamSynchronize(st) != hipSuccess || !ok) return set_error(TKV_IO_ERROR, "WAL index copy to the device failed");
+  return rw;
+}
+
+// tkv_wal_salvage_device behind its argument checks. The loop of the salvage program: index the
+// sub-image [p, size) (the index kernels unchanged: images at any byte alignment are theirs), make its
+// offsets absolute, open a gap at its stop s, resynchronise from s + 1, close the gap there, go on.
+int salvage_device_any(const uint8_t* d_wal, uint64_t size, uint64_t* d_off64, uint64_t cap, uint64_t* h_gaps,
+                       uint64_t gap_cap, uint64_t max_gaps, uint64_t* n_records, uint64_t* n_gaps, uint64_t* stop_offset,
+                       uint64_t* bytes_skipped, uint64_t* max_sequence, hipStream_t st) {
+  std::uint64_t* last = wal_salvage_last();
+  std::fill(last, last + 6, 0);
+  *n_records = *n_gaps = *bytes_skipped = *max_sequence = 0;
+  *stop_offset = size;
+  std::uint64_t p = 0;
+  while (p < size) {
+    const std::uint64_t have = std::min(*n_records, cap);
+    std::uint64_t ng = 0, stop = 0, mseq = 0;
+    bool walked = false;
+    last[5] += 1;
+    const int rc = index_device_any(d_wal + p, size - p, cap > have ? d_off64 + have : nullptr, nullptr, cap - have, &ng, &stop,
+                                    &mseq, st, &walked);
+    if (rc != TKV_OK && rc != TKV_CORRUPTED) return rc;
+    if (int e = wal_salvage_add_base(d_off64 + have, std::min(ng, cap - have), p, st)) return e;
+    *n_records += ng;
+    *max_sequence = std::max(*max_sequence, mseq);
+    if (rc == TKV_OK) break;
+    const std::uint64_t s = p + stop;  // an invalid position
+    // no further resynchronisation: the budget is used up, or this sub-image went to the exact host walk
+    if (*n_gaps == max_gaps || walked) {
+      *stop_offset = s;
+      break;
+    }
+    std::uint64_t q = size;
+    const int rr = wal_resync_device_impl(d_wal, size, s + 1, &q, st);
+    if (rr != TKV_OK && rr != TKV_NOT_FOUND) return rr;
+    if (*n_gaps < gap_cap) {
+      h_gaps[2 * *n_gaps] = s;
+      h_gaps[2 * *n_gaps + 1] = q;
+    }
+    *n_gaps += 1;
+    *bytes_skipped += q - s;
+    p = q;
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) return set_error(TKV_IO_ERROR, "WAL salvage: stream synchronize failed");
+  return *n_gaps == 0 && *stop_offset == size ? TKV_OK : TKV_CORRUPTED;
+}
+
+// Per-device buffers of tkv_wal_salvage, as the host-image index keeps its own: the device copy of the
+// image and of the offsets, grown by doubling and kept between calls up to kSalvageKeep bytes each, and
+// the stream the salvage of a host image runs on (guarded by mu, held for the whole call).
+constexpr std::uint64_t kSalvageKeep = std::uint64_t(256) << 20;
+struct SalvageHost {
+  std::mutex mu;
+  void* d_img = nullptr;
+  void* d_off = nullptr;
+  std::uint64_t cap_img = 0, cap_off = 0;
+  hipStream_t st = nullptr;
+  ~SalvageHost() {
+    (void)hipFree(d_img);
+    (void)hipFree(d_off);
+    if (st) (void)hipStreamDestroy(st);
+  }
+};
+
 int sst_check(const std::uint64_t* h_sizes, std::uint64_t n) {
   for (std::uint64_t i = 0; i < n; ++i)
     if (h_sizes[i] < TKV_SST_MIN_IMAGE || h_sizes[i] > 0xFFFFFFFFull)
@@ -260,30 +354,8 @@ int tkv_wal_index_device(const uint8_t* d_wal, uint64_t size, uint64_t* d_off64,
     return set_error(TKV_INVALID_ARGUMENT, "cap > 0 without an offsets array");
   if (ptr_ok(d_off32) && size > 0xFFFFFFFFull + 1ull)
     return set_error(TKV_INVALID_ARGUMENT, "image larger than 4 GiB (u32 offsets)");
-  *n_good = *stop_offset = *max_sequence = 0;
-  if (size == 0) return TKV_OK;
-  bool host_walk = false;
-  const int rc = wal_index_device_impl(d_wal, size, d_off64, d_off32, cap, n_good, stop_offset, max_sequence,
-                                       static_cast<hipStream_t>(stream), &host_walk);
-  if (!host_walk) return rc;
-  // the verify's exact fallback (tkv_wal_verify_device): its walk's positions go to the caller's arrays,
-  // the copies on the caller's stream
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  std::vector<std::uint8_t> h(size);
-  if (hipMemcpyAsync(h.data(), d_wal, size, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return set_error(TKV_IO_ERROR, "WAL image copy to host failed");
-  std::vector<std::uint64_t> pos;
-  const int rw = wal_verify_host_walk(h.data(), size, n_good, stop_offset, &pos);
-  if (rw != TKV_OK && rw != TKV_CORRUPTED) return rw;
-  *max_sequence = max_sequence_of(h.data(), pos);
-  const std::size_t n = static_cast<std::size_t>(std::min<std::uint64_t>(pos.size(), cap));
-  std::vector<std::uint32_t> p32;
-  if (n && ptr_ok(d_off32)) p32.assign(pos.begin(), pos.begin() + static_cast<std::ptrdiff_t>(n));
-  bool ok = true;
-  if (n && ptr_ok(d_off64)) ok = hipMemcpyAsync(d_off64, pos.data(), n * 8, hipMemcpyHostToDevice, st) == hipSuccess;
-  if (ok && n && ptr_ok(d_off32)) ok = hipMemcpyAsync(d_off32, p32.data(), n * 4, hipMemcpyHostToDevice, st) == hipSuccess;
-  if (hipStreamSynchronize(st) != hipSuccess || !ok) return set_error(TKV_IO_ERROR, "WAL index copy to the device failed");
-  return rw;
+  return index_device_any(d_wal, size, d_off64, d_off32, cap, n_good, stop_offset, max_sequence,
+                          static_cast<hipStream_t>(stream), nullptr);
 }
 
 int tkv_wal_index(const uint8_t* h_wal, uint64_t size, uint64_t* h_off64, uint64_t cap, uint64_t* n_good,
@@ -303,6 +375,77 @@ int tkv_wal_index(const uint8_t* h_wal, uint64_t size, uint64_t* h_off64, uint64
   const std::size_t n = static_cast<std::size_t>(std::min<std::uint64_t>(pos.size(), cap));
   if (n) std::memcpy(h_off64, pos.data(), n * 8);
   return rw;
+}
+
+int tkv_wal_resync_device(const uint8_t* d_wal, uint64_t size, uint64_t from, uint64_t* found, void* stream) {
+  if ((size && !ptr_ok(d_wal)) || !ptr_ok(found)) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  if (from > size) return set_error(TKV_INVALID_ARGUMENT, "resync start behind the image's end");
+  std::uint64_t* last = wal_salvage_last();
+  std::fill(last, last + 6, 0);
+  return wal_resync_device_impl(d_wal, size, from, found, static_cast<hipStream_t>(stream));
+}
+
+int tkv_wal_salvage_device(const uint8_t* d_wal, uint64_t size, uint64_t* d_off64, uint64_t cap, uint64_t* h_gaps,
+                           uint64_t gap_cap, uint64_t max_gaps, uint64_t* n_records, uint64_t* n_gaps,
+                           uint64_t* stop_offset, uint64_t* bytes_skipped, uint64_t* max_sequence, void* stream) {
+  if ((size && !ptr_ok(d_wal)) || !ptr_ok(n_records) || !ptr_ok(n_gaps) || !ptr_ok(stop_offset) || !ptr_ok(bytes_skipped) ||
+      !ptr_ok(max_sequence))
+    return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  if (cap && !ptr_ok(d_off64)) return set_error(TKV_INVALID_ARGUMENT, "cap > 0 without an offsets array");
+  if (gap_cap && !ptr_ok(h_gaps)) return set_error(TKV_INVALID_ARGUMENT, "gap_cap > 0 without a gaps array");
+  if (size == 0) {
+    *n_records = *n_gaps = *stop_offset = *bytes_skipped = *max_sequence = 0;
+    return TKV_OK;
+  }
+  return salvage_device_any(d_wal, size, d_off64, cap, h_gaps, gap_cap, max_gaps, n_records, n_gaps, stop_offset,
+                            bytes_skipped, max_sequence, static_cast<hipStream_t>(stream));
+}
+
+int tkv_wal_salvage(const uint8_t* h_wal, uint64_t size, uint64_t* h_off64, uint64_t cap, uint64_t* h_gaps,
+                    uint64_t gap_cap, uint64_t max_gaps, uint64_t* n_records, uint64_t* n_gaps, uint64_t* stop_offset,
+                    uint64_t* bytes_skipped, uint64_t* max_sequence) {
+  if ((size && !ptr_ok(h_wal)) || !ptr_ok(n_records) || !ptr_ok(n_gaps) || !ptr_ok(stop_offset) || !ptr_ok(bytes_skipped) ||
+      !ptr_ok(max_sequence))
+    return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  if (cap && !ptr_ok(h_off64)) return set_error(TKV_INVALID_ARGUMENT, "cap > 0 without an offsets array");
+  if (gap_cap && !ptr_ok(h_gaps)) return set_error(TKV_INVALID_ARGUMENT, "gap_cap > 0 without a gaps array");
+  *n_records = *n_gaps = *stop_offset = *bytes_skipped = *max_sequence = 0;
+  if (size == 0) return TKV_OK;
+  // the device copy of the image and of the offsets (a good record is at least 26 bytes long)
+  const std::uint64_t dcap = std::min<std::uint64_t>(cap, size / kWalMeta);
+  SalvageHost* hp = nullptr;
+  if (int rc = per_device(&hp)) return rc;
+  SalvageHost& h = *hp;
+  std::lock_guard<std::mutex> lk(h.mu);
+  if (!h.st && hipStreamCreateWithFlags(&h.st, hipStreamNonBlocking) != hipSuccess)
+    return set_error(TKV_IO_ERROR, "WAL salvage: no stream");
+  if (grow(&h.d_img, &h.cap_img, size, 1) != TKV_OK || grow(&h.d_off, &h.cap_off, dcap, 8) != TKV_OK) {
+    // The device cannot hold it: the index's exact host walk, and no resynchronisation.
+    (void)hipGetLastError();
+    return tkv_wal_index(h_wal, size, h_off64, cap, n_records, stop_offset, max_sequence);
+  }
+  auto* d_off = static_cast<std::uint64_t*>(h.d_off);
+  int rc = wal_host_image_stage_impl(h_wal, size, static_cast<std::uint8_t*>(h.d_img));
+  if (rc == TKV_OK)
+    rc = salvage_device_any(static_cast<const std::uint8_t*>(h.d_img), size, d_off, dcap, h_gaps, gap_cap, max_gaps, n_records,
+                            n_gaps, stop_offset, bytes_skipped, max_sequence, h.st);
+  const std::uint64_t n = std::min(*n_records, dcap);
+  if ((rc == TKV_OK || rc == TKV_CORRUPTED) && n &&
+      (hipMemcpyAsync(h_off64, d_off, n * 8, hipMemcpyDeviceToHost, h.st) != hipSuccess || hipStreamSynchronize(h.st) != hipSuccess))
+    rc = set_error(TKV_IO_ERROR, "WAL salvage: offsets copy to the host failed");
+  // nothing of the call outlives it; buffers larger than kSalvageKeep are released, as the index's are
+  (void)hipStreamSynchronize(h.st);
+  if (h.cap_img > kSalvageKeep) {
+    (void)hipFree(h.d_img);
+    h.d_img = nullptr;
+    h.cap_img = 0;
+  }
+  if (h.cap_off * 8 > kSalvageKeep) {
+    (void)hipFree(h.d_off);
+    h.d_off = nullptr;
+    h.cap_off = 0;
+  }
+  return rc;
 }
 
 }  // extern "C"

@@ -39,6 +39,24 @@ int wal_index_host_image_impl(const std::uint8_t* h_wal, std::uint64_t size, std
                               std::uint64_t* n_good, std::uint64_t* stop_offset, std::uint64_t* max_sequence,
                               bool* needs_host_walk);
 
+// The host image [h_wal, h_wal + size) into the caller's device buffer d_dst, as the host-image verify
+// and index copy theirs (pinned sources in one copy, pageable ones through the pinned staging slabs);
+// synchronous.
+int wal_host_image_stage_impl(const std::uint8_t* h_wal, std::uint64_t size, std::uint8_t* d_dst);
+
+// WAL resynchronisation on `st` (tkv_wal_resync.hip; synchronous): *found = the smallest p >= from
+// (from <= size, checked by the caller) at which a record passes every check of wal_entry::decode,
+// TKV_OK; or *found = size, TKV_NOT_FOUND. Counts into wal_salvage_last().
+int wal_resync_device_impl(const std::uint8_t* d_wal, std::uint64_t size, std::uint64_t from, std::uint64_t* found,
+                           hipStream_t st);
+
+// d_off64[0, n) += base on `st` (asynchronous): a sub-image's index offsets made absolute.
+int wal_salvage_add_base(std::uint64_t* d_off64, std::uint64_t n, std::uint64_t base, hipStream_t st);
+
+// The calling thread's six salvage counters (tkv_debug_wal_salvage_last): resynchronisations, search
+// spans, start offsets tested, candidates folded, their payload bytes, index calls.
+std::uint64_t* wal_salvage_last();
+
 // WAL group-commit encode on `st` (tkv_wal_encode.hip; synchronous): the size scan, the host's
 // overflow / invalid decision from its pinned result, then the emit into [d_img, d_img + total) with the
 // CRC of every record of record_len <= 240 folded in the same pass and the longer ones stamped by one

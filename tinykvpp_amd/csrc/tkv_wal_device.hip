@@ -1582,6 +1582,34 @@ constexpr std::uint64_t kStageSlab = std::uint64_t(64) << 20;
 // Device copies of host images up to this size stay allocated between verifies.
 constexpr std::uint64_t kKeepImg = std::uint64_t(256) << 20;
 
+// The host image into d_dst (a device buffer of at least `size` bytes) on s.st; synchronous.
+int host_image_stage_locked(WalScratch& s, const std::uint8_t* h_wal, std::uint64_t size, std::uint8_t* d_dst) {
+  hipPointerAttribute_t attr;
+  const bool pinned = hipPointerGetAttributes(&attr, h_wal) == hipSuccess && attr.type == hipMemoryTypeHost;
+  if (!pinned) (void)hipGetLastError();
+  if (pinned) {
+    TKV_HIP_RC(hipMemcpyAsync(d_dst, h_wal, size, hipMemcpyHostToDevice, s.st));
+  } else {
+    // pageable: host threads fill one pinned slab while the copy engine drains the other
+    for (int i = 0; i < 2; ++i) {
+      if (!s.slab[i]) {
+        TKV_HIP_RC(hipHostMalloc(reinterpret_cast<void**>(&s.slab[i]), kStageSlab, hipHostMallocDefault));
+        TKV_HIP_RC(hipEventCreateWithFlags(&s.slab_free[i], hipEventDisableTiming));
+      }
+    }
+    int k = 0;
+    for (std::uint64_t off = 0; off < size; off += kStageSlab, k ^= 1) {
+      const std::uint64_t m = std::min(kStageSlab, size - off);
+      TKV_HIP_RC(hipEventSynchronize(s.slab_free[k]));
+      stage_copy(s.slab[k], h_wal + off, m);
+      TKV_HIP_RC(hipMemcpyAsync(d_dst + off, s.slab[k], m, hipMemcpyHostToDevice, s.st));
+      TKV_HIP_RC(hipEventRecord(s.slab_free[k], s.st));
+    }
+  }
+  TKV_HIP_RC(hipStreamSynchronize(s.st));
+  return TKV_OK;
+}
+
 // The host image into the device buffer s.d_img (synchronous). *needs_host_walk: the device cannot hold it.
 int host_image_copy_locked(WalScratch& s, const std::uint8_t* h_wal, std::uint64_t size, bool* needs_host_walk) {
   if (size > s.cap_img) {
@@ -1597,30 +1625,7 @@ int host_image_copy_locked(WalScratch& s, const std::uint8_t* h_wal, std::uint64
     }
     s.cap_img = size;
   }
-  hipPointerAttribute_t attr;
-  const bool pinned = hipPointerGetAttributes(&attr, h_wal) == hipSuccess && attr.type == hipMemoryTypeHost;
-  if (!pinned) (void)hipGetLastError();
-  if (pinned) {
-    TKV_HIP_RC(hipMemcpyAsync(s.d_img, h_wal, size, hipMemcpyHostToDevice, s.st));
-  } else {
-    // pageable: host threads fill one pinned slab while the copy engine drains the other
-    for (int i = 0; i < 2; ++i) {
-      if (!s.slab[i]) {
-        TKV_HIP_RC(hipHostMalloc(reinterpret_cast<void**>(&s.slab[i]), kStageSlab, hipHostMallocDefault));
-        TKV_HIP_RC(hipEventCreateWithFlags(&s.slab_free[i], hipEventDisableTiming));
-      }
-    }
-    int k = 0;
-    for (std::uint64_t off = 0; off < size; off += kStageSlab, k ^= 1) {
-      const std::uint64_t m = std::min(kStageSlab, size - off);
-      TKV_HIP_RC(hipEventSynchronize(s.slab_free[k]));
-      stage_copy(s.slab[k], h_wal + off, m);
-      TKV_HIP_RC(hipMemcpyAsync(s.d_img + off, s.slab[k], m, hipMemcpyHostToDevice, s.st));
-      TKV_HIP_RC(hipEventRecord(s.slab_free[k], s.st));
-    }
-  }
-  TKV_HIP_RC(hipStreamSynchronize(s.st));
-  return TKV_OK;
+  return host_image_stage_locked(s, h_wal, size, s.d_img);
 }
 
 int host_image_locked(WalScratch& s, const std::uint8_t* h_wal, std::uint64_t size, std::uint64_t* n_good,
@@ -1692,6 +1697,17 @@ int wal_verify_host_image_impl(const std::uint8_t* h_wal, std::uint64_t size, st
     s.d_img = nullptr;
     s.cap_img = 0;
   }
+  return rc;
+}
+
+int wal_host_image_stage_impl(const std::uint8_t* h_wal, std::uint64_t size, std::uint8_t* d_dst) {
+  if (size == 0) return TKV_OK;
+  WalScratch* sp = nullptr;
+  if (int rc = scratch(&sp)) return rc;
+  WalScratch& s = *sp;
+  std::lock_guard<std::mutex> lk(s.mu);
+  const int rc = host_image_stage_locked(s, h_wal, size, d_dst);
+  (void)hipStreamSynchronize(s.st);  // no copy that reads the caller's buffer outlives the call
   return rc;
 }
 

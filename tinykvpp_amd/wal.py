@@ -349,12 +349,136 @@ def decode_device(image, rec_off, size=None, key_views=False, val_views=False, s
     return WalBatch(*cols, keys, vals)
 
 
-def recover_device(image, size=None, key_views=False, val_views=False, stream=None):
+MODES = ("strict", "tolerate_tail", "skip_corrupted")
+_NO_LIMIT = (1 << 64) - 1
+
+
+def _device_image(image, size):
+    import torch
+    if image.dtype != torch.uint8 or not image.is_cuda or not image.is_contiguous():
+        raise ValueError("image must be a contiguous uint8 CUDA tensor")
+    n = image.numel() if size is None else int(size)
+    if n > image.numel():
+        raise ValueError("size exceeds the tensor")
+    return n
+
+
+def resync_device(image, start, size=None, stream=None):
+    """The smallest position >= ``start`` of a WAL image in a uint8 CUDA tensor (first ``size`` bytes;
+    default all) at which a record passes every check of wal_entry::decode (length inside the image, key
+    and value inside the record, CRC), or None when there is none (tkv_wal_resync_device). Every byte
+    offset is a candidate; a CRC collision (2^-32 per plausible header) is accepted. Synchronous on
+    ``stream``."""
+    from ._lib import NOT_FOUND
+    from .crc32 import _check_data, _launch_stream
+    n = _device_image(image, size)
+    _check_data(image)
+    found = ctypes.c_uint64(0)
+    rc = load_library().tkv_wal_resync_device(ctypes.c_void_p(image.data_ptr()) if n else None, n, int(start),
+                                              ctypes.byref(found), _launch_stream(stream, image.device))
+    if rc == NOT_FOUND:
+        return None
+    check(rc)
+    return found.value
+
+
+GAPS_CAP = 1 << 16  # gaps a salvage wrapper lists in its first (and nearly always only) call: a 1 MiB array
+
+
+def _gaps_array(call, size):
+    """Runs call(gaps array, gap_cap) -> (rc, n_gaps) with room for every gap the image can hold (a gap
+    is at least one byte and, but for a tail gap, is followed by a record of at least 26 bytes), at most
+    GAPS_CAP. Only an image with more gaps than GAPS_CAP is salvaged a second time, with room for all."""
+    cap = max(1, min(size // (kMetadataSize + 1) + 1, GAPS_CAP))
+    gaps = np.zeros((cap, 2), np.uint64)
+    rc, k = call(gaps, cap)
+    if rc in (OK, CORRUPTED) and k > cap:
+        gaps = np.zeros((k, 2), np.uint64)
+        rc, k = call(gaps, k)
+    return rc, gaps[:k]
+
+
+def salvage_device(image, size=None, out=None, max_gaps=None, stream=None):
+    """Every valid record of a WAL image in a uint8 CUDA tensor, corrupted ranges skipped
+    (tkv_wal_salvage_device): the sequential program ``p = 0; while p < size: valid(p) ? emit, p += record
+    size : p += 1``. Returns (status, offsets, gaps, stop_offset, max_sequence): offsets is ``out[:n]``, an
+    int64 CUDA tensor of the salvaged records' start offsets in increasing order (allocated with
+    size // 26 entries when not given), gaps a (k, 2) uint64 numpy array of the skipped ranges
+    [start, end) (end == size: a tail gap), status "ok" when there is no gap and the image was read to its
+    end. ``max_gaps`` bounds the resynchronisations: the call stops at the next invalid position, which is
+    stop_offset (else size); 0 is index_device. Valid records nested in a corrupted record's value are
+    salvaged, by the definition; the caller decides what to do with the gaps."""
+    import torch
+    from .crc32 import _check_data, _check_vec, _launch_stream
+    n = _device_image(image, size)
+    _check_data(image)
+    if out is None:
+        out = torch.empty(n // kMetadataSize, dtype=torch.int64, device=image.device)
+        if stream is not None and stream != torch.cuda.current_stream(image.device):
+            out.record_stream(stream)
+    _check_vec("out", out, torch.int64, 0, image.device)
+    cap = out.numel()
+    st = _launch_stream(stream, image.device)
+    nrec, ngap, stop, skipped, seq = (ctypes.c_uint64(0) for _ in range(5))
+    limit = _NO_LIMIT if max_gaps is None else int(max_gaps)
+
+    def call(gaps, gap_cap):
+        rc = load_library().tkv_wal_salvage_device(
+            ctypes.c_void_p(image.data_ptr()) if n else None, n, ctypes.c_void_p(out.data_ptr()) if cap else None, cap,
+            ctypes.c_void_p(gaps.ctypes.data), gap_cap, limit, ctypes.byref(nrec), ctypes.byref(ngap),
+            ctypes.byref(stop), ctypes.byref(skipped), ctypes.byref(seq), st)
+        return rc, ngap.value
+    rc, gaps = _gaps_array(call, n)
+    if rc not in (OK, CORRUPTED):
+        check(rc)
+    if nrec.value > cap:
+        raise ValueError(f"out holds {cap} offsets, the image has {nrec.value} valid records")
+    return ("ok" if rc == OK else "corrupted"), out[:nrec.value], gaps, stop.value, seq.value
+
+
+def salvage(wal_bytes, max_gaps=None):
+    """salvage_device for a slurped WAL image on the host (tkv_wal_salvage): copied to the device as
+    index() copies it and salvaged there. Returns (status, offsets, gaps, stop_offset, max_sequence) with
+    offsets a uint64 numpy array. An image the device cannot hold gets index()'s result (no
+    resynchronisation, stop_offset at its stop)."""
+    buf = _host_image(wal_bytes)
+    cap = buf.size // kMetadataSize
+    offs = np.empty(cap, np.uint64)
+    nrec, ngap, stop, skipped, seq = (ctypes.c_uint64(0) for _ in range(5))
+    limit = _NO_LIMIT if max_gaps is None else int(max_gaps)
+
+    def call(gaps, gap_cap):
+        rc = load_library().tkv_wal_salvage(
+            ctypes.c_void_p(buf.ctypes.data) if buf.size else None, buf.size,
+            ctypes.c_void_p(offs.ctypes.data) if cap else None, cap, ctypes.c_void_p(gaps.ctypes.data), gap_cap, limit,
+            ctypes.byref(nrec), ctypes.byref(ngap), ctypes.byref(stop), ctypes.byref(skipped), ctypes.byref(seq))
+        return rc, ngap.value
+    rc, gaps = _gaps_array(call, buf.size)
+    if rc not in (OK, CORRUPTED):
+        check(rc)
+    return ("ok" if rc == OK else "corrupted"), offs[:nrec.value], gaps, stop.value, seq.value
+
+
+def recover_device(image, size=None, key_views=False, val_views=False, stream=None, mode="strict"):
     """What engine::create's recovery loop (engine.cpp:31-53) consumes, for a WAL image in HBM:
     index_device, then decode_device on the good records. Returns (status, WalBatch, stop_offset,
     max_sequence); status, stop_offset and max_sequence are index_device's, the batch holds exactly the
-    good prefix."""
+    good prefix.
+
+    ``mode`` picks the recovery policy. "strict" (default) is the above, the reference's only one.
+    "tolerate_tail": when the index reports corrupted and no valid record follows its stop offset
+    (resync_device(stop + 1) finds none: a torn tail), the result is the good prefix with status "ok";
+    otherwise the strict result. "skip_corrupted": every salvaged record is decoded (salvage_device),
+    status "corrupted" when there was a gap, and the gaps are returned as a fifth element."""
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {MODES}")
+    if mode == "skip_corrupted":
+        status, offs, gaps, stop, max_seq = salvage_device(image, size=size, stream=stream)
+        batch = decode_device(image, offs, size=size, key_views=key_views, val_views=val_views, stream=stream)
+        return status, batch, stop, max_seq, gaps
     status, offs, stop, max_seq = index_device(image, size=size, stream=stream)
+    if mode == "tolerate_tail" and status == "corrupted" and resync_device(image, stop + 1, size=size, stream=stream) is None:
+        status = "ok"
     batch = decode_device(image, offs, size=size, key_views=key_views, val_views=val_views, stream=stream)
     return status, batch, stop, max_seq
 
@@ -397,11 +521,23 @@ def decode_batch(wal_bytes, rec_off, key_views=False, val_views=False):
     return WalBatch(*cols, keys, vals)
 
 
-def recover(wal_bytes, key_views=False, val_views=False):
+def recover(wal_bytes, key_views=False, val_views=False, mode="strict"):
     """recover_device for a slurped WAL image on the host: index() (verify and list on the GPU), then
     decode_batch (host threads) on the good records. Returns (status, WalBatch of numpy arrays,
-    stop_offset, max_sequence)."""
+    stop_offset, max_sequence). ``mode`` as recover_device: "tolerate_tail" asks salvage() with one
+    resynchronisation whether a valid record follows the stop offset, "skip_corrupted" decodes every
+    salvaged record and appends the gaps."""
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {MODES}")
+    if mode == "skip_corrupted":
+        status, offs, gaps, stop, max_seq = salvage(wal_bytes)
+        return status, decode_batch(wal_bytes, offs, key_views=key_views, val_views=val_views), stop, max_seq, gaps
     status, offs, stop, max_seq = index(wal_bytes)
+    if mode == "tolerate_tail" and status == "corrupted":
+        # one resynchronisation: a torn tail is a single gap that ends at the image's end, no record behind it
+        _, more, gaps, _, _ = salvage(wal_bytes, max_gaps=1)
+        if more.size == offs.size and gaps.shape[0] == 1 and int(gaps[0, 1]) == _host_image(wal_bytes).size:
+            status = "ok"
     return status, decode_batch(wal_bytes, offs, key_views=key_views, val_views=val_views), stop, max_seq
 
 
