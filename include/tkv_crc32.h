@@ -387,6 +387,64 @@ int tkv_sst_stamp_footer(const uint8_t *h_index, uint64_t index_size, uint8_t *h
 /* Check the stored crc32_ of h_footer against the index image: TKV_OK or TKV_CORRUPTED. */
 int tkv_sst_verify_footer(const uint8_t *h_index, uint64_t index_size, const uint8_t *h_footer);
 
+/* ---- SSTable flush: data blocks, index and footer in one call ------------------- */
+
+/* The writer loop sstable_writer::append / is_data_block_complete / get_data_block / record_data_block /
+ * get_index / get_footer (sstable_writer.cpp) for n entries held as arenas: internal key i is
+ * [keys + key_off[i], + key_len[i]), value i is [vals + val_off[i], + val_len[i]). Entries are taken in
+ * the order given; the call neither sorts them nor checks their order, as the reference writer does
+ * not. Sources may have any alignment, may have gaps and may overlap each other (many entries may share
+ * one key); they do not overlap the destination. val_len == NULL: every value is empty (vals / val_off
+ * ignored).
+ * Sizes. kl, vl = the lengths of entry i, vlen(x) = the bytes of LEB128(x). append counts
+ * e_i = 8 + kl + vl per entry (sstable_writer.cpp:61,122) while write_string twice writes
+ * w_i = vlen(kl) + kl + vlen(vl) + vl. S and W are the exclusive prefix sums of e and w.
+ * Cut (append, then is_data_block_complete: size >= target, sstable_writer.cpp:127-129): b_0 = 0 and
+ * b_{j+1} = the smallest m > b_j with S[m] - S[b_j] >= target_block_size, or n when there is none (the
+ * trailing partial block). Block j holds the c_j entries [b_j, b_{j+1}) and counts z_j = S[b_{j+1}] -
+ * S[b_j] bytes; B = the number of blocks.
+ * Block image j, 36 + z_j bytes at file offset O_j = 36 * j + S[b_j], is the image the stamping section
+ * above defines: 0x14 | u32 c_j | u32 z_j | u32 z_j | u8 0 | 3 zero bytes | u32 crc32_ | varint(z_j) |
+ * the entries back to back as varint(kl) | key | varint(vl) | value (entry i at O_j + 21 + vlen(z_j) +
+ * W[i] - W[b_j]) | zeros up to 36 + z_j (the slack between what is counted and what is written, and the
+ * image padding). crc32_ is the stamp of tkv_sst_stamp_blocks.
+ * Index image at index_offset = 36 * B + S[n]: u64 B, then per block varint(kl of entry b_j) | that key |
+ * u64 O_j | u64 (36 + z_j) (get_index). Footer, 20 bytes directly behind the index: u32 index_offset |
+ * u32 index_size | u32 0 | u32 0 | u32 crc32_, crc32_ the stamp of tkv_sst_stamp_footer.
+ * file_size = index_offset + index_size + 20. All integers little-endian.
+ * d_file may have any byte alignment; no byte outside [d_file, d_file + file_size) is written or
+ * read-modify-written. *file_size, *n_blocks, *index_offset and *index_size are set whenever the
+ * arguments are valid. file_size > cap, or n_blocks > block_cap with any block array non-NULL:
+ * TKV_BUFFER_OVERFLOW with the four sizes set and nothing written to d_file or a block array (cap = 0
+ * with d_file = NULL and NULL block arrays is the sizing call). Block arrays (device, each nullable,
+ * block_cap entries): block_off[j] = O_j, block_size[j] = 36 + z_j, block_first[j] = b_j; the first two
+ * are valid inputs of tkv_sst_block_crcs_device, and widened to u64 of tkv_sst_verify_blocks.
+ * TKV_INVALID_ARGUMENT, decided before any byte is written and without reading a source byte, the four
+ * sizes untouched: n == 0 (the reference writer verifies a non-empty block and index); n > 2^32 - 1;
+ * target_block_size == 0; NULL where a pointer is required (keys, key_off, key_len, the four size
+ * outputs; vals and val_off with val_len; d_file with cap > 0); some kl or vl >= 2^28 (its varint
+ * would take 5 bytes where 4 are counted, and the body would overrun its counted size); some
+ * 36 + z_j > 2^32 - 1 (the header fields are u32); file_size > 2^32 - 1 (the footer fields are u32).
+ * The device call is synchronous on `stream` (the host needs the sizes before the emit); with no usable
+ * GPU it returns TKV_IO_ERROR. No CRC is computed on the CPU and no image byte crosses PCIe. */
+int tkv_sst_build_device(const uint8_t *d_keys, const uint64_t *d_key_off, const uint32_t *d_key_len,
+                         const uint8_t *d_vals, const uint64_t *d_val_off, const uint32_t *d_val_len,
+                         uint64_t n, uint32_t target_block_size,
+                         uint8_t *d_file, uint64_t cap,
+                         uint64_t *d_block_off, uint32_t *d_block_size, uint32_t *d_block_first, uint64_t block_cap,
+                         uint64_t *file_size, uint64_t *n_blocks, uint64_t *index_offset, uint64_t *index_size,
+                         void *stream);
+
+/* The same with every pointer in HOST memory. The cut and the layout (CRC fields zero) are computed on
+ * host threads; the stamps come from the paths tkv_sst_stamp_blocks and tkv_sst_stamp_footer use.
+ * Sizing, overflow and argument errors are decided before any GPU call. */
+int tkv_sst_build(const uint8_t *h_keys, const uint64_t *h_key_off, const uint32_t *h_key_len,
+                  const uint8_t *h_vals, const uint64_t *h_val_off, const uint32_t *h_val_len,
+                  uint64_t n, uint32_t target_block_size,
+                  uint8_t *h_file, uint64_t cap,
+                  uint64_t *h_block_off, uint32_t *h_block_size, uint32_t *h_block_first, uint64_t block_cap,
+                  uint64_t *file_size, uint64_t *n_blocks, uint64_t *index_offset, uint64_t *index_size);
+
 /* ---- CRC-32C (Castagnoli) — SURVEY.md §8f rank 4 ------------------------------------------------ */
 
 /* Same engine and kernels with the tables of the Castagnoli polynomial (reflected 0x82F63B78,
@@ -546,6 +604,29 @@ void tkv_debug_wal_salvage_geometry(uint64_t out[4]);
  * resynchronisations, out[1] = search spans launched, out[2] = start offsets tested, out[3] = candidates
  * whose CRC was computed, out[4] = payload bytes folded for them, out[5] = index calls. */
 void tkv_debug_wal_salvage_last(uint64_t out[6]);
+/* The cut and the layout of tkv_sst_build alone (host only, no GPU): the file image with every CRC
+ * field zero, the sizes and the block arrays. Arguments, status codes and what is left untouched on an
+ * error are tkv_sst_build's. */
+int tkv_debug_sst_build_layout(const uint8_t *h_keys, const uint64_t *h_key_off, const uint32_t *h_key_len,
+                               const uint8_t *h_vals, const uint64_t *h_val_off, const uint32_t *h_val_len,
+                               uint64_t n, uint32_t target_block_size, uint8_t *h_file, uint64_t cap,
+                               uint64_t *h_block_off, uint32_t *h_block_size, uint32_t *h_block_first,
+                               uint64_t block_cap, uint64_t *file_size, uint64_t *n_blocks, uint64_t *index_offset,
+                               uint64_t *index_size);
+/* Geometry of tkv_sst_build_device: out[0] = file bytes per emit tile, out[1] = entries per workgroup of
+ * the scans, out[2] = entries whose hops the block cut composes in LDS before the doubling rounds (0:
+ * plain doubling over the entries), out[3] = 0. */
+void tkv_debug_sst_build_geometry(uint64_t out[4]);
+/* What the calling thread's last tkv_sst_build_device did: out[0] = data blocks, out[1] = doubling
+ * rounds of the block cut, out[2] = emit waves, out[3] = file bytes (all 0 when it wrote nothing). */
+void tkv_debug_sst_build_last(uint64_t out[4]);
+/* Phase times of the calling thread's last tkv_sst_build_device, in milliseconds between device events
+ * on its stream: out_ms[0] = size scans, out_ms[1] = block cut and index layout (with the host's read of
+ * the scan result in front), out_ms[2] = positions, tiles, emit and index (with the host's read of the
+ * cut's result in front), out_ms[3] = CRC batch and stamp. All 0 unless timing was enabled before that
+ * call. `enable` switches the timing of this thread's later calls on or off (default off: no events are
+ * created); returns the previous setting. out_ms may be NULL. */
+int tkv_debug_sst_build_phases(int enable, double out_ms[4]);
 
 #ifdef __cplusplus
 }

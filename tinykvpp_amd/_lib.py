@@ -76,6 +76,15 @@ SIGNATURES = {
     "tkv_sst_block_crcs_device": (_int, [_u8p, _vp, _vp, _vp, _u64, _int, _vp]),
     "tkv_sst_stamp_footer": (_int, [_u8p, _u64, _vp]),
     "tkv_sst_verify_footer": (_int, [_u8p, _u64, _vp]),
+    "tkv_sst_build_device": (_int, [_u8p, _vp, _vp, _u8p, _vp, _vp, _u64, _u32, _u8p, _u64, _vp, _vp, _vp, _u64] +
+                             [ctypes.POINTER(_u64)] * 4 + [_vp]),
+    "tkv_sst_build": (_int, [_u8p, _vp, _vp, _u8p, _vp, _vp, _u64, _u32, _u8p, _u64, _vp, _vp, _vp, _u64] +
+                      [ctypes.POINTER(_u64)] * 4),
+    "tkv_debug_sst_build_layout": (_int, [_u8p, _vp, _vp, _u8p, _vp, _vp, _u64, _u32, _u8p, _u64, _vp, _vp, _vp, _u64] +
+                                   [ctypes.POINTER(_u64)] * 4),
+    "tkv_debug_sst_build_geometry": (None, [_vp]),
+    "tkv_debug_sst_build_last": (None, [_vp]),
+    "tkv_debug_sst_build_phases": (_int, [_int, _vp]),
     "tkv_crc32c_update": (_int, [_u32, _vp, _sz, ctypes.POINTER(_u32)]),
     "tkv_crc32c_update_device": (_int, [_u32, _vp, _sz, _vp, _vp]),
     "tkv_crc32c_batch_device": (_int, [_u8p, _vp, _vp, _vp, _vp, _u64, _vp]),
@@ -119,7 +128,9 @@ OPTIONAL = {"tkv_build_id", "tkv_wal_index_device", "tkv_wal_index", "tkv_debug_
             "tkv_debug_wal_encode_geometry", "tkv_debug_wal_encode_last", "tkv_debug_set_wal_encode_fused",
             "tkv_wal_decode_device", "tkv_wal_decode_host", "tkv_debug_wal_decode_geometry",
             "tkv_debug_wal_decode_last", "tkv_wal_resync_device", "tkv_wal_salvage_device", "tkv_wal_salvage",
-            "tkv_debug_wal_salvage_geometry", "tkv_debug_wal_salvage_last"}
+            "tkv_debug_wal_salvage_geometry", "tkv_debug_wal_salvage_last", "tkv_sst_build_device", "tkv_sst_build",
+            "tkv_debug_sst_build_layout", "tkv_debug_sst_build_geometry", "tkv_debug_sst_build_last",
+            "tkv_debug_sst_build_phases"}
 
 _lib = None
 

@@ -38,4 +38,15 @@ int device_cu_count();
 hipError_t launch_sst_fix(std::uint8_t* file, const std::uint64_t* offsets, const std::uint32_t* sizes,
                           std::uint32_t* out, std::uint64_t n, int store, const DeviceTables* tabs, hipStream_t st);
 
+// tkv_sst_build.hip: the SSTable flush on `st` (synchronous): size scans, the exact block cut by pointer
+// doubling, the host's invalid / overflow decision from a pinned result, the tile emit of blocks, index
+// and footer with zero CRC fields, one CRC batch and the stamp. Arguments and results are
+// tkv_sst_build_device's (n >= 1, target_block_size >= 1 and the required pointers checked by the caller).
+int sst_build_device_impl(const std::uint8_t* d_keys, const std::uint64_t* d_key_off, const std::uint32_t* d_key_len,
+                          const std::uint8_t* d_vals, const std::uint64_t* d_val_off, const std::uint32_t* d_val_len,
+                          std::uint64_t n, std::uint32_t target_block_size, std::uint8_t* d_file, std::uint64_t cap,
+                          std::uint64_t* d_block_off, std::uint32_t* d_block_size, std::uint32_t* d_block_first,
+                          std::uint64_t block_cap, std::uint64_t* file_size, std::uint64_t* n_blocks,
+                          std::uint64_t* index_offset, std::uint64_t* index_size, hipStream_t st);
+
 }  // namespace tkv

@@ -17,6 +17,7 @@
 #include "tkv_crc32.h"
 #include "tkv_device_util.h"
 #include "tkv_engine.h"
+#include "tkv_sst_layout.h"
 #include "tkv_wal_device.h"
 #include "tkv_wal_layout.h"
 
@@ -865,6 +866,188 @@ int tkv_sst_verify_footer(const uint8_t* h_index, uint64_t index_size, const uin
   if (int rc = footer_crc(h_index, index_size, h_footer, &crc)) return rc;
   std::memcpy(&stored, h_footer + TKV_SST_FOOTER_CRC_OFFSET, 4);
   return stored == crc ? TKV_OK : set_error(TKV_CORRUPTED, "corrupted SSTable index or footer");
+}
+
+}  // extern "C"
+
+namespace {
+// ---- SSTable flush (sstable_writer::append ... get_footer for a whole entry list) ---------------------
+struct SstIn {
+  const std::uint8_t* keys;
+  const std::uint64_t* key_off;
+  const std::uint32_t* key_len;
+  const std::uint8_t* vals;
+  const std::uint64_t* val_off;
+  const std::uint32_t* val_len;
+  std::uint64_t n;
+  std::uint32_t T;
+};
+struct SstOut {
+  std::uint8_t* file;
+  std::uint64_t cap;
+  std::uint64_t* block_off;
+  std::uint32_t* block_size;
+  std::uint32_t* block_first;
+  std::uint64_t block_cap;
+  std::uint64_t *file_size, *n_blocks, *index_offset, *index_size;
+};
+// The cut and the layout of a host entry list.
+struct SstPlan {
+  std::vector<std::uint64_t> pos;     // file offset of every entry
+  std::vector<std::uint32_t> first;   // b_j, B + 1 entries
+  std::vector<std::uint64_t> off;     // O_j
+  std::vector<std::uint32_t> size;    // 36 + z_j
+  std::uint64_t index_offset = 0, index_size = 0, file_size = 0;
+};
+
+// The argument checks both entry points share.
+int sst_build_check(const SstIn& in, const SstOut& o) {
+  if (in.n == 0) return set_error(TKV_INVALID_ARGUMENT, "SSTable build: no entries");
+  if (in.n > 0xFFFFFFFFull) return set_error(TKV_INVALID_ARGUMENT, "SSTable build: more than 2^32 - 1 entries");
+  if (in.T == 0) return set_error(TKV_INVALID_ARGUMENT, "SSTable build: target_block_size is 0");
+  if (!ptr_ok(in.keys) || !ptr_ok(in.key_off) || !ptr_ok(in.key_len) ||
+      (ptr_ok(in.val_len) && (!ptr_ok(in.vals) || !ptr_ok(in.val_off))) || !ptr_ok(o.file_size) || !ptr_ok(o.n_blocks) ||
+      !ptr_ok(o.index_offset) || !ptr_ok(o.index_size) || (o.cap && !ptr_ok(o.file)))
+    return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  return TKV_OK;
+}
+
+// Sizes, the greedy cut (append, then is_data_block_complete: size >= target) and every offset; no
+// source byte is read.
+int sst_build_plan(const SstIn& in, SstPlan& p) {
+  for (std::uint64_t i = 0; i < in.n; ++i)
+    if (in.key_len[i] >= kSstMaxLen || (in.val_len && in.val_len[i] >= kSstMaxLen))
+      return set_error(TKV_INVALID_ARGUMENT, "SSTable build: a key or value length is 2^28 or more");
+  p.pos.resize(in.n);
+  std::uint64_t file = 0, b = 0;
+  while (b < in.n) {
+    std::uint64_t z = 0, m = b;
+    while (m < in.n && z < in.T) {
+      z += sst_counted(in.key_len[m], in.val_len ? in.val_len[m] : 0u);
+      ++m;
+    }
+    if (kSstOverhead + z > 0xFFFFFFFFull) return set_error(TKV_INVALID_ARGUMENT, "SSTable build: a data block does not fit u32");
+    std::uint64_t at = file + kSstHeader + sst_vlen(z);
+    for (std::uint64_t i = b; i < m; ++i) {
+      p.pos[i] = at;
+      at += sst_written(in.key_len[i], in.val_len ? in.val_len[i] : 0u);
+    }
+    p.first.push_back(static_cast<std::uint32_t>(b));
+    p.off.push_back(file);
+    p.size.push_back(static_cast<std::uint32_t>(kSstOverhead + z));
+    file += kSstOverhead + z;
+    b = m;
+  }
+  p.first.push_back(static_cast<std::uint32_t>(in.n));
+  p.index_offset = file;
+  p.index_size = 8;
+  for (std::size_t j = 0; j + 1 < p.first.size(); ++j) {
+    const std::uint32_t kl = in.key_len[p.first[j]];
+    p.index_size += std::uint64_t(sst_vlen(kl)) + kl + kSstIndexFixed;
+  }
+  p.file_size = p.index_offset + p.index_size + kSstFooter;
+  if (p.file_size > 0xFFFFFFFFull) return set_error(TKV_INVALID_ARGUMENT, "SSTable build: the file does not fit u32");
+  return TKV_OK;
+}
+
+// The file image with every CRC field zero, entries on host threads.
+void sst_build_layout(const SstIn& in, const SstPlan& p, std::uint8_t* f) {
+  const std::uint64_t B = p.off.size();
+  std::memset(f, 0, p.index_offset);  // slack and padding
+  parallel_for(B, [&](std::uint64_t j) {
+    std::uint8_t h[32];
+    const std::uint32_t nh = sst_block_head(h, p.first[j + 1] - p.first[j], p.size[j] - kSstOverhead);
+    std::memcpy(f + p.off[j], h, nh);
+  });
+  parallel_for(in.n, [&](std::uint64_t i) {
+    std::uint8_t* d = f + p.pos[i];
+    const std::uint32_t kl = in.key_len[i], vl = in.val_len ? in.val_len[i] : 0u;
+    d += sst_put_varint(d, kl);
+    if (kl) std::memcpy(d, in.keys + in.key_off[i], kl);
+    d += kl;
+    d += sst_put_varint(d, vl);
+    if (vl) std::memcpy(d, in.vals + in.val_off[i], vl);
+  });
+  std::uint8_t* d = f + p.index_offset;
+  for (int b = 0; b < 8; ++b) *d++ = static_cast<std::uint8_t>(B >> (8 * b));
+  for (std::uint64_t j = 0; j < B; ++j) {
+    const std::uint64_t i = p.first[j];
+    const std::uint32_t kl = in.key_len[i];
+    d += sst_put_varint(d, kl);
+    if (kl) std::memcpy(d, in.keys + in.key_off[i], kl);
+    d += kl;
+    const std::uint64_t sz = p.size[j];
+    for (int b = 0; b < 8; ++b) *d++ = static_cast<std::uint8_t>(p.off[j] >> (8 * b));
+    for (int b = 0; b < 8; ++b) *d++ = static_cast<std::uint8_t>(sz >> (8 * b));
+  }
+  const std::uint32_t foot[5] = {static_cast<std::uint32_t>(p.index_offset), static_cast<std::uint32_t>(p.index_size), 0u, 0u, 0u};
+  for (int k = 0; k < 5; ++k)
+    for (int b = 0; b < 4; ++b) *d++ = static_cast<std::uint8_t>(foot[k] >> (8 * b));
+}
+
+// Checks, the plan, the sizes, overflow, the layout and the block arrays of a host build.
+int sst_build_host_layout(const SstIn& in, const SstOut& o, SstPlan& p) {
+  if (int rc = sst_build_check(in, o)) return rc;
+  if (int rc = sst_build_plan(in, p)) return rc;
+  const std::uint64_t B = p.off.size();
+  *o.file_size = p.file_size;
+  *o.n_blocks = B;
+  *o.index_offset = p.index_offset;
+  *o.index_size = p.index_size;
+  const bool want_blocks = ptr_ok(o.block_off) || ptr_ok(o.block_size) || ptr_ok(o.block_first);
+  if (p.file_size > o.cap || (want_blocks && B > o.block_cap))
+    return set_error(TKV_BUFFER_OVERFLOW, "SSTable build: the file or the block arrays do not fit");
+  if (!ptr_ok(o.file)) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  sst_build_layout(in, p, o.file);
+  if (ptr_ok(o.block_off)) std::memcpy(o.block_off, p.off.data(), B * sizeof(std::uint64_t));
+  if (ptr_ok(o.block_size)) std::memcpy(o.block_size, p.size.data(), B * sizeof(std::uint32_t));
+  if (ptr_ok(o.block_first)) std::memcpy(o.block_first, p.first.data(), B * sizeof(std::uint32_t));
+  return TKV_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tkv_sst_build_device(const uint8_t* d_keys, const uint64_t* d_key_off, const uint32_t* d_key_len, const uint8_t* d_vals,
+                         const uint64_t* d_val_off, const uint32_t* d_val_len, uint64_t n, uint32_t target_block_size,
+                         uint8_t* d_file, uint64_t cap, uint64_t* d_block_off, uint32_t* d_block_size,
+                         uint32_t* d_block_first, uint64_t block_cap, uint64_t* file_size, uint64_t* n_blocks,
+                         uint64_t* index_offset, uint64_t* index_size, void* stream) {
+  const SstIn in{d_keys, d_key_off, d_key_len, d_vals, d_val_off, d_val_len, n, target_block_size};
+  const SstOut o{d_file, cap, d_block_off, d_block_size, d_block_first, block_cap, file_size, n_blocks, index_offset, index_size};
+  if (int rc = sst_build_check(in, o)) return rc;
+  return sst_build_device_impl(d_keys, d_key_off, d_key_len, d_vals, d_val_off, d_val_len, n, target_block_size, d_file, cap,
+                               d_block_off, d_block_size, d_block_first, block_cap, file_size, n_blocks, index_offset,
+                               index_size, static_cast<hipStream_t>(stream));
+}
+
+int tkv_sst_build(const uint8_t* h_keys, const uint64_t* h_key_off, const uint32_t* h_key_len, const uint8_t* h_vals,
+                  const uint64_t* h_val_off, const uint32_t* h_val_len, uint64_t n, uint32_t target_block_size,
+                  uint8_t* h_file, uint64_t cap, uint64_t* h_block_off, uint32_t* h_block_size, uint32_t* h_block_first,
+                  uint64_t block_cap, uint64_t* file_size, uint64_t* n_blocks, uint64_t* index_offset,
+                  uint64_t* index_size) {
+  const SstIn in{h_keys, h_key_off, h_key_len, h_vals, h_val_off, h_val_len, n, target_block_size};
+  const SstOut o{h_file, cap, h_block_off, h_block_size, h_block_first, block_cap, file_size, n_blocks, index_offset, index_size};
+  SstPlan p;
+  if (int rc = sst_build_host_layout(in, o, p)) return rc;
+  // the stamps of tkv_sst_stamp_blocks and tkv_sst_stamp_footer: the fields are zero, so the plain CRC
+  // of an image is its stamp
+  const std::uint64_t B = p.off.size();
+  std::vector<std::uint32_t> crc(B);
+  if (int rc = batch_host_impl(kAlgoCrc32, h_file, p.off.data(), p.size.data(), nullptr, crc.data(), B)) return rc;
+  parallel_for(B, [&](std::uint64_t j) { std::memcpy(h_file + p.off[j] + TKV_SST_CRC_OFFSET, &crc[j], 4); });
+  return tkv_sst_stamp_footer(h_file + p.index_offset, p.index_size, h_file + p.index_offset + p.index_size);
+}
+
+int tkv_debug_sst_build_layout(const uint8_t* h_keys, const uint64_t* h_key_off, const uint32_t* h_key_len,
+                               const uint8_t* h_vals, const uint64_t* h_val_off, const uint32_t* h_val_len, uint64_t n,
+                               uint32_t target_block_size, uint8_t* h_file, uint64_t cap, uint64_t* h_block_off,
+                               uint32_t* h_block_size, uint32_t* h_block_first, uint64_t block_cap, uint64_t* file_size,
+                               uint64_t* n_blocks, uint64_t* index_offset, uint64_t* index_size) {
+  const SstIn in{h_keys, h_key_off, h_key_len, h_vals, h_val_off, h_val_len, n, target_block_size};
+  const SstOut o{h_file, cap, h_block_off, h_block_size, h_block_first, block_cap, file_size, n_blocks, index_offset, index_size};
+  SstPlan p;
+  return sst_build_host_layout(in, o, p);
 }
 
 size_t tkv_debug_wal_chain(const uint8_t* h_wal, uint64_t size, uint64_t* out_pos, size_t cap, uint64_t* end,

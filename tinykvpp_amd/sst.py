@@ -143,3 +143,160 @@ def verify_footer(index_image, footer):
     if rc not in (OK, CORRUPTED):
         check(rc)
     return "ok" if rc == OK else "corrupted"
+
+
+# ---- flush: data blocks, index and footer in one call (include/tkv_crc32.h "SSTable flush") ---------
+class BuiltTable:
+    """What build_device / build return: ``file`` (the file image, ``size`` bytes), the data blocks'
+    ``block_off`` / ``block_size`` / ``block_first`` (offset, image size and first entry of every block)
+    and where the index lies."""
+
+    __slots__ = ("file", "size", "block_off", "block_size", "block_first", "index_offset", "index_size")
+
+    def __init__(self, file, size, block_off, block_size, block_first, index_offset, index_size):
+        self.file, self.size = file, size
+        self.block_off, self.block_size, self.block_first = block_off, block_size, block_first
+        self.index_offset, self.index_size = index_offset, index_size
+
+    @property
+    def n_blocks(self):
+        return len(self.block_off)
+
+
+def build_device(keys, key_off, key_len, vals=None, val_off=None, val_len=None, target_block_size=4096, out=None,
+                 stream=None):
+    """The writer loop for entries held on the device (tkv_sst_build_device): ``keys`` / ``vals`` uint8
+    CUDA arenas, ``key_off`` / ``val_off`` int64 and ``key_len`` / ``val_len`` int32 (u32 values) CUDA
+    tensors with one entry per element, the dtypes wal.decode_device returns. Entries are written in the
+    order given (the caller sorts and builds the internal keys). Makes the sizing call, then the build
+    into ``out[:size]`` (a uint8 CUDA tensor of any alignment; allocated when not given). Returns a
+    BuiltTable of CUDA tensors: file uint8, block_off int64, block_size / block_first int32 (u32 values).
+    An ``out`` that is too small raises with the size needed. Synchronous on ``stream``."""
+    import torch
+    from ._lib import BUFFER_OVERFLOW
+    from .crc32 import _check_data, _check_vec, _launch_stream
+    if keys.dtype != torch.uint8:
+        raise ValueError("keys must be a uint8 tensor")
+    _check_data(keys)
+    dev = keys.device
+    n = key_len.numel()
+    _check_vec("key_off", key_off, torch.int64, n, dev)
+    _check_vec("key_len", key_len, torch.int32, n, dev)
+    if val_len is not None:
+        if vals is None or val_off is None:
+            raise ValueError("val_len needs vals and val_off")
+        _check_vec("vals", vals, torch.uint8, 0, dev)
+        _check_vec("val_off", val_off, torch.int64, n, dev)
+        _check_vec("val_len", val_len, torch.int32, n, dev)
+    other = stream is not None and stream != torch.cuda.current_stream(dev)
+
+    def alloc(count, dtype):
+        t = torch.empty(count, dtype=dtype, device=dev)
+        if other:
+            t.record_stream(stream)
+        return t
+
+    def ptr(t):
+        return None if t is None else ctypes.c_void_p(t.data_ptr())
+    lib = load_library()
+    st = _launch_stream(stream, dev)
+    sizes = [ctypes.c_uint64(0) for _ in range(4)]  # file_size, n_blocks, index_offset, index_size
+
+    def call(file, cap, boff, bsize, bfirst, bcap):
+        return lib.tkv_sst_build_device(ptr(keys), ptr(key_off), ptr(key_len), ptr(vals) if val_len is not None else None,
+                                        ptr(val_off) if val_len is not None else None, ptr(val_len), n,
+                                        int(target_block_size), file, cap, boff, bsize, bfirst, bcap,
+                                        *[ctypes.byref(s) for s in sizes], st)
+    rc = call(None, 0, None, None, None, 0)  # the sizing call
+    if rc not in (OK, BUFFER_OVERFLOW):
+        check(rc)
+    size, nb = sizes[0].value, sizes[1].value
+    if out is None:
+        out = alloc(size, torch.uint8)
+    _check_vec("out", out, torch.uint8, 0, dev)
+    if out.numel() < size:
+        raise ValueError(f"out holds {out.numel()} bytes, the file needs {size}")
+    boff, bsize, bfirst = alloc(nb, torch.int64), alloc(nb, torch.int32), alloc(nb, torch.int32)
+    check(call(ptr(out), out.numel(), ptr(boff), ptr(bsize), ptr(bfirst), nb))
+    return BuiltTable(out[:size], size, boff, bsize, bfirst, sizes[2].value, sizes[3].value)
+
+
+def build(entries, target_block_size=4096):
+    """The same on the host (tkv_sst_build): ``entries`` is [(ikey, value), ...] or a tuple of numpy arrays
+    (keys uint8, key_off uint64, key_len uint32, vals uint8, val_off uint64, val_len uint32). The cut and
+    the layout run on host threads, the stamps on the GPU. Returns a BuiltTable of numpy arrays (file
+    uint8, block_off uint64, block_size / block_first uint32)."""
+    from ._lib import BUFFER_OVERFLOW
+    if isinstance(entries, tuple):
+        keys, koff, klen, vals, voff, vlen = entries
+        keys, vals = (np.ascontiguousarray(a, dtype=np.uint8) for a in (keys, vals))
+        koff, voff = (np.ascontiguousarray(a, dtype=np.uint64) for a in (koff, voff))
+        klen, vlen = (np.ascontiguousarray(a, dtype=np.uint32) for a in (klen, vlen))
+    else:
+        from .wal import _arena
+        keys, koff, klen = _arena([k for k, _ in entries])
+        vals, voff, vlen = _arena([v for _, v in entries])
+    n = klen.size
+    lib = load_library()
+    sizes = [ctypes.c_uint64(0) for _ in range(4)]
+
+    def ptr(a):
+        return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+    def call(file, cap, boff, bsize, bfirst, bcap):
+        return lib.tkv_sst_build(ptr(keys), ptr(koff), ptr(klen), ptr(vals), ptr(voff), ptr(vlen), n,
+                                 int(target_block_size), ptr(file), cap, ptr(boff), ptr(bsize), ptr(bfirst), bcap,
+                                 *[ctypes.byref(s) for s in sizes])
+    rc = call(None, 0, None, None, None, 0)  # the sizing call
+    if rc not in (OK, BUFFER_OVERFLOW):
+        check(rc)
+    size, nb = sizes[0].value, sizes[1].value
+    file = np.empty(size, np.uint8)
+    boff, bsize, bfirst = np.empty(nb, np.uint64), np.empty(nb, np.uint32), np.empty(nb, np.uint32)
+    check(call(file, size, boff, bsize, bfirst, nb))
+    return BuiltTable(file, size, boff, bsize, bfirst, sizes[2].value, sizes[3].value)
+
+
+def _read_varint(buf, pos):
+    v = shift = 0
+    while True:
+        if pos >= len(buf) or shift > 63:
+            raise ValueError("truncated varint in the index image")
+        b = buf[pos]
+        pos += 1
+        v |= (b & 0x7F) << shift
+        shift += 7
+        if b < 0x80:
+            return v, pos
+
+
+def read_index(file):
+    """Open a built file again (pure Python, no GPU): parse the footer at the file's end, check its
+    crc32_ over index image || footer[0:16] and the index's framing, and return
+    [(smallest_key, offset, size)], the input of verify_blocks. Raises ValueError when the footer, its
+    checksum or the index does not hold."""
+    import zlib
+    buf = bytes(file.tobytes() if isinstance(file, np.ndarray) else file)
+    if len(buf) < FOOTER_SIZE + 8:
+        raise ValueError("file shorter than an index and a footer")
+    ioff, isz, _, _, crc = struct.unpack("<IIIII", buf[-FOOTER_SIZE:])
+    if ioff + isz + FOOTER_SIZE != len(buf) or isz < 8:
+        raise ValueError("footer does not describe this file")
+    if zlib.crc32(buf[ioff:ioff + isz + FOOTER_CRC_OFFSET]) != crc:
+        raise ValueError("corrupted SSTable index or footer")
+    idx = buf[ioff:ioff + isz]
+    (count,) = struct.unpack_from("<Q", idx, 0)
+    pos, out = 8, []
+    for _ in range(count):
+        kl, pos = _read_varint(idx, pos)
+        if pos + kl + 16 > len(idx):
+            raise ValueError("index entry reaches past the index image")
+        key = idx[pos:pos + kl]
+        off, size = struct.unpack_from("<QQ", idx, pos + kl)
+        if off + size > ioff:
+            raise ValueError("index entry reaches past the data blocks")
+        out.append((key, off, size))
+        pos += kl + 16
+    if pos != len(idx):
+        raise ValueError("bytes left behind the last index entry")
+    return out
