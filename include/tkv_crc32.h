@@ -445,6 +445,76 @@ int tkv_sst_build(const uint8_t *h_keys, const uint64_t *h_key_off, const uint32
                   uint64_t *h_block_off, uint32_t *h_block_size, uint32_t *h_block_first, uint64_t block_cap,
                   uint64_t *file_size, uint64_t *n_blocks, uint64_t *index_offset, uint64_t *index_size);
 
+/* ---- SSTable scan: verify, index and entries of a file image in one call ---------- */
+
+/* The reader of what tkv_sst_build[_device] writes, in the same columnar form: its outputs are valid
+ * inputs of tkv_sst_build_device, its input is what that call writes. The reference leaves this half open
+ * (decode_data_block_header and decode_data_block are stubs, sstable_reader::read_data_block returns an
+ * empty block), so, like the stamps, what a reader checks is this library's decision, written down here.
+ * Checks, in this order of precedence. All arithmetic is 64-bit; no byte outside [file, file + file_size)
+ * is read, whatever the file holds; a length that failed a check is never used to copy or to walk.
+ * Footer (else TKV_CORRUPTED with *bad_block = TKV_SST_BAD_FOOTER): 28 <= file_size <= 2^32 - 1; the last
+ * 20 bytes are u32 index_offset | u32 index_size | u32 bloom_offset | u32 bloom_size | u32 crc32_ with
+ * index_offset + index_size + 20 == file_size and index_size >= 8 (the bloom fields are not interpreted);
+ * crc32_ equals the CRC-32 of [index_offset, index_offset + index_size + 16) (tkv_sst_verify_footer).
+ * Index (else TKV_CORRUPTED, TKV_SST_BAD_INDEX): B = the u64 at the index start, B <= (index_size - 8) /
+ * 17; then B entries varint(kl) | key | u64 off | u64 size, each length varint ending within 4 bytes
+ * (value < 2^28; a redundant encoding such as 80 00 is taken at its value, as a LEB128 reader takes it),
+ * each entry inside the index, size >= TKV_SST_MIN_IMAGE and off + size <= index_offset; the position
+ * behind entry B - 1 is exactly index_size. B == 0 is a valid empty table: TKV_OK, all sizes 0. Blocks
+ * need not tile the data region and may be listed in any order.
+ * Block j, image [off_j, off_j + size_j): any failure makes block j bad and *bad_block is the smallest
+ * bad j. Byte 0 is 0x14; c = the u32 at 1, z = the u32 at 5, the u32 at 9 equals z, byte 13 is 0 (the
+ * three pad bytes are covered by the checksum only); 36 + z == size_j; c >= 1 and 8 c <= z; the varint
+ * at byte 21 ends within 5 bytes and has the value z: the body is the z bytes behind it; the u32 at 17
+ * equals the stamp (the CRC of the image with that field read as zero, tkv_sst_block_crcs_device's
+ * value); the walk of c entries varint(kl) | key | varint(vl) | value from the body's start stays inside
+ * the body, every varint ending within 4 bytes and inside the body; the sum of 8 + kl + vl over the c
+ * entries equals z; the index entry's key equals the first entry's key, in length and bytes. Bytes
+ * behind the last entry (slack and padding) are not inspected: the reference leaves arena bytes there.
+ * Outputs, all in the index's order (block j's entries in front of block j + 1's): block_off / block_size
+ * / block_first as tkv_sst_build_device's block arrays; key_len / val_len the lengths. Without a views
+ * flag the spans are copied back to back into d_keys / d_vals, key_off / val_off are the exclusive u64
+ * prefix sums of the lengths and *keys_size / *vals_size the totals. With a views flag nothing is copied
+ * for that arena: the offsets point into the file image, the arena and its cap are ignored, the total is
+ * still reported. Every output array is nullable and then skipped (a NULL arena is not written).
+ * Destinations may have any byte alignment; nothing outside [d_keys, d_keys + *keys_size) and [d_vals,
+ * d_vals + *vals_size) is written or read-modify-written.
+ * TKV_CORRUPTED: *bad_block is set, the four sizes are 0, nothing is written to any output array.
+ * TKV_OK: *bad_block = *n_blocks. TKV_BUFFER_OVERFLOW: the sizes are set and no array is written, when
+ * *n_entries > entry_cap with any entry column non-NULL, *n_blocks > block_cap with any block array
+ * non-NULL, or a copied arena's total is over its cap (all caps 0 with NULL arrays is the sizing call; it
+ * returns TKV_OK for a table without a key or value byte). TKV_INVALID_ARGUMENT, decided before any
+ * device work: NULL file with file_size > 0, unknown flag bits, NULL among the five scalar outputs,
+ * file_size > 2^32 - 1. file_size < 28 is TKV_CORRUPTED with TKV_SST_BAD_FOOTER, not an argument error.
+ * The device call is synchronous on `stream`; with no usable GPU it returns TKV_IO_ERROR; a scratch
+ * allocation that fails returns TKV_OUT_OF_MEMORY (the scratch holds 24 bytes per index byte, 52 per block
+ * and 40 per entry). No CRC is computed on the CPU and no file byte crosses PCIe: only a small pinned
+ * result block does. */
+#define TKV_SST_SCAN_KEY_VIEWS 1u   /* keys stay in the file image */
+#define TKV_SST_SCAN_VAL_VIEWS 2u   /* values stay in the file image */
+#define TKV_SST_BAD_FOOTER UINT64_MAX         /* *bad_block when the footer (or its checksum) fails */
+#define TKV_SST_BAD_INDEX  (UINT64_MAX - 1)   /* *bad_block when the index framing fails */
+int tkv_sst_scan_device(const uint8_t *d_file, uint64_t file_size, uint32_t flags,
+                        uint64_t *d_key_off, uint32_t *d_key_len, uint64_t *d_val_off, uint32_t *d_val_len,
+                        uint64_t entry_cap,
+                        uint8_t *d_keys, uint64_t keys_cap, uint8_t *d_vals, uint64_t vals_cap,
+                        uint64_t *d_block_off, uint32_t *d_block_size, uint32_t *d_block_first, uint64_t block_cap,
+                        uint64_t *n_entries, uint64_t *n_blocks, uint64_t *keys_size, uint64_t *vals_size,
+                        uint64_t *bad_block, void *stream);
+
+/* The same contract for a host image, every pointer in HOST memory. Parsing and copies run on host
+ * threads, one task per range of blocks; the checksums go through the paths tkv_sst_verify_footer and
+ * tkv_sst_verify_blocks use. Argument errors and footer failures, apart from the footer's checksum, are
+ * decided before any GPU call. */
+int tkv_sst_scan(const uint8_t *h_file, uint64_t file_size, uint32_t flags,
+                 uint64_t *h_key_off, uint32_t *h_key_len, uint64_t *h_val_off, uint32_t *h_val_len,
+                 uint64_t entry_cap,
+                 uint8_t *h_keys, uint64_t keys_cap, uint8_t *h_vals, uint64_t vals_cap,
+                 uint64_t *h_block_off, uint32_t *h_block_size, uint32_t *h_block_first, uint64_t block_cap,
+                 uint64_t *n_entries, uint64_t *n_blocks, uint64_t *keys_size, uint64_t *vals_size,
+                 uint64_t *bad_block);
+
 /* ---- CRC-32C (Castagnoli) — SURVEY.md §8f rank 4 ------------------------------------------------ */
 
 /* Same engine and kernels with the tables of the Castagnoli polynomial (reflected 0x82F63B78,
@@ -627,6 +697,32 @@ void tkv_debug_sst_build_last(uint64_t out[4]);
  * call. `enable` switches the timing of this thread's later calls on or off (default off: no events are
  * created); returns the previous setting. out_ms may be NULL. */
 int tkv_debug_sst_build_phases(int enable, double out_ms[4]);
+/* tkv_sst_scan with every checksum comparison skipped (host only, no GPU): the parse and the copies
+ * alone, the counterpart of tkv_debug_sst_build_layout. Arguments, status codes and what is left
+ * untouched on an error are tkv_sst_scan's. */
+int tkv_debug_sst_scan_parse(const uint8_t *h_file, uint64_t file_size, uint32_t flags,
+                             uint64_t *h_key_off, uint32_t *h_key_len, uint64_t *h_val_off, uint32_t *h_val_len,
+                             uint64_t entry_cap,
+                             uint8_t *h_keys, uint64_t keys_cap, uint8_t *h_vals, uint64_t vals_cap,
+                             uint64_t *h_block_off, uint32_t *h_block_size, uint32_t *h_block_first,
+                             uint64_t block_cap,
+                             uint64_t *n_entries, uint64_t *n_blocks, uint64_t *keys_size, uint64_t *vals_size,
+                             uint64_t *bad_block);
+/* Geometry of tkv_sst_scan_device: out[0] = body bytes a parse window is walked for, out[1] = bytes of
+ * varint look-ahead behind them, out[2] = arena bytes per emit tile, out[3] = entries per workgroup of the
+ * scans. */
+void tkv_debug_sst_scan_geometry(uint64_t out[4]);
+/* What the calling thread's last tkv_sst_scan_device did: out[0] = data blocks, out[1] = doubling rounds
+ * of the index chain, out[2] = parse waves, out[3] = emit waves of both arenas (all 0 when it did not
+ * reach its end). */
+void tkv_debug_sst_scan_last(uint64_t out[4]);
+/* Phase times of the calling thread's last tkv_sst_scan_device that returned TKV_OK, in milliseconds
+ * between device events on its stream: out_ms[0] = open (footer fields, index chain, ranks, block list,
+ * with the host's read of the footer in front), out_ms[1] = checksum (the CRC batch and the comparison),
+ * out_ms[2] = parse (both passes and the count scan, with the host's read of the verdict between them),
+ * out_ms[3] = emit (length scans, columns, arena gathers). Switch and return value as
+ * tkv_debug_sst_build_phases. */
+int tkv_debug_sst_scan_phases(int enable, double out_ms[4]);
 
 #ifdef __cplusplus
 }

@@ -49,4 +49,16 @@ int sst_build_device_impl(const std::uint8_t* d_keys, const std::uint64_t* d_key
                           std::uint64_t block_cap, std::uint64_t* file_size, std::uint64_t* n_blocks,
                           std::uint64_t* index_offset, std::uint64_t* index_size, hipStream_t st);
 
+// tkv_sst_scan.hip: the SSTable scan on `st` (synchronous): the footer's fields, the index chain by
+// pointer doubling, one CRC batch over the block images and the footer's span, the wave-per-block parse
+// through LDS windows, the host's corrupted / overflow decision from a pinned result, the records and the
+// arena emit. Arguments and results are tkv_sst_scan_device's (pointers, flags and 28 <= file_size <=
+// 2^32 - 1 checked by the caller).
+int sst_scan_device_impl(const std::uint8_t* d_file, std::uint64_t file_size, std::uint32_t flags, std::uint64_t* d_key_off,
+                         std::uint32_t* d_key_len, std::uint64_t* d_val_off, std::uint32_t* d_val_len, std::uint64_t entry_cap,
+                         std::uint8_t* d_keys, std::uint64_t keys_cap, std::uint8_t* d_vals, std::uint64_t vals_cap,
+                         std::uint64_t* d_block_off, std::uint32_t* d_block_size, std::uint32_t* d_block_first,
+                         std::uint64_t block_cap, std::uint64_t* n_entries, std::uint64_t* n_blocks, std::uint64_t* keys_size,
+                         std::uint64_t* vals_size, std::uint64_t* bad_block, hipStream_t st);
+
 }  // namespace tkv

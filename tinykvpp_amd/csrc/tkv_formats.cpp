@@ -1060,3 +1060,254 @@ size_t tkv_debug_wal_chain(const uint8_t* h_wal, uint64_t size, uint64_t* out_po
 }
 
 }  // extern "C"
+
+namespace {
+// ---- SSTable scan (the reader of what tkv_sst_build writes; include/tkv_crc32.h "SSTable scan") --------
+struct ScanIn {
+  const std::uint8_t* file;
+  std::uint64_t size;
+  std::uint32_t flags;
+};
+struct ScanOut {
+  std::uint64_t* key_off;
+  std::uint32_t* key_len;
+  std::uint64_t* val_off;
+  std::uint32_t* val_len;
+  std::uint64_t entry_cap;
+  std::uint8_t* keys;
+  std::uint64_t keys_cap;
+  std::uint8_t* vals;
+  std::uint64_t vals_cap;
+  std::uint64_t* block_off;
+  std::uint32_t* block_size;
+  std::uint32_t* block_first;
+  std::uint64_t block_cap;
+  std::uint64_t *n_entries, *n_blocks, *keys_size, *vals_size, *bad_block;
+};
+
+// The argument checks both entry points share: decided before any device work.
+int sst_scan_check(const ScanIn& in, const ScanOut& o) {
+  if ((in.size && !ptr_ok(in.file)) || !ptr_ok(o.n_entries) || !ptr_ok(o.n_blocks) || !ptr_ok(o.keys_size) ||
+      !ptr_ok(o.vals_size) || !ptr_ok(o.bad_block))
+    return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  if (in.flags & ~(TKV_SST_SCAN_KEY_VIEWS | TKV_SST_SCAN_VAL_VIEWS)) return set_error(TKV_INVALID_ARGUMENT, "SSTable scan: unknown flag");
+  if (in.size > 0xFFFFFFFFull) return set_error(TKV_INVALID_ARGUMENT, "SSTable scan: the file does not fit u32");
+  return TKV_OK;
+}
+
+int sst_scan_corrupted(const ScanOut& o, std::uint64_t bad, const char* msg) {
+  *o.bad_block = bad;
+  *o.n_entries = *o.n_blocks = *o.keys_size = *o.vals_size = 0;
+  return set_error(TKV_CORRUPTED, msg);
+}
+
+// The min(avail, maxb) bytes at p as a word: no byte behind p + avail is read.
+std::uint64_t bytes_word(const std::uint8_t* p, std::uint64_t avail, std::uint32_t maxb) {
+  std::uint64_t w = 0;
+  for (std::uint32_t k = 0; k < maxb && k < avail; ++k) w |= static_cast<std::uint64_t>(p[k]) << (8u * k);
+  return w;
+}
+std::uint64_t le_bytes(const std::uint8_t* p, int n) {
+  std::uint64_t v = 0;
+  for (int b = 0; b < n; ++b) v |= static_cast<std::uint64_t>(p[b]) << (8 * b);
+  return v;
+}
+
+struct ScanBlock {
+  std::uint64_t off, size;   // the image
+  std::uint64_t ikey;        // file offset of the index entry's key
+  std::uint32_t ikl;
+};
+struct ScanRec {
+  std::uint64_t kpos, vpos;  // file offsets of the key's and the value's bytes
+  std::uint32_t kl, vl;
+};
+
+// Block b's checks (all but the checksum) and its walk: the entry count, or 0 when a check fails (a
+// valid block holds at least one entry). rec != nullptr: the c records are written there.
+std::uint32_t sst_scan_block(const std::uint8_t* file, const ScanBlock& b, ScanRec* rec) {
+  const std::uint8_t* img = file + b.off;
+  const std::uint32_t c = static_cast<std::uint32_t>(le_bytes(img + 1, 4)), z = static_cast<std::uint32_t>(le_bytes(img + 5, 4));
+  const std::uint64_t vavail = b.size - kSstHeader;
+  const SstVarint zv = sst_varint_word(bytes_word(img + kSstHeader, vavail, kSstBodyLenBytes), vavail, kSstBodyLenBytes);
+  if (!sst_block_header_ok(img[0], c, z, static_cast<std::uint32_t>(le_bytes(img + 9, 4)), img[13], b.size, zv)) return 0;
+  const std::uint8_t* body = img + kSstHeader + zv.n;
+  const std::uint64_t bpos = b.off + kSstHeader + zv.n;
+  std::uint64_t q = 0, sum = 0, kq = 0;
+  std::uint32_t kl = 0;
+  for (std::uint32_t r = 0; r < 2u * c; ++r) {
+    if (q >= z) return 0;
+    const SstLink s = sst_chain_next(static_cast<std::uint32_t>(bytes_word(body + q, z - q, kSstLenBytes)), q, z, 0u);
+    if (!s.ok) return 0;
+    if (!(r & 1u)) {
+      kq = q + s.n;
+      kl = s.len;
+      if (r == 0 && (kl != b.ikl || (kl && std::memcmp(body + kq, file + b.ikey, kl) != 0))) return 0;
+    } else {
+      sum += sst_counted(kl, s.len);
+      if (rec) rec[r >> 1] = ScanRec{bpos + kq, bpos + q + s.n, kl, s.len};
+    }
+    q = s.next;
+  }
+  return sum == z ? c : 0u;
+}
+
+// fn(t, lo, hi) for the ranges [lo, hi) of [0, n) on host threads: one task per range of blocks.
+template <class F>
+void parallel_ranges(std::uint64_t n, F fn) {
+  const unsigned nt = n >= 64 ? static_cast<unsigned>(std::min<std::uint64_t>(host_threads(), n / 32)) : 1u;
+  if (nt <= 1) {
+    fn(0u, std::uint64_t(0), n);
+    return;
+  }
+  std::vector<std::thread> th;
+  for (unsigned t = 0; t < nt; ++t) th.emplace_back([=] { fn(t, n * t / nt, n * (t + 1) / nt); });
+  for (auto& t : th) t.join();
+}
+
+// The scan of a host image; crc = false skips every checksum comparison (tkv_debug_sst_scan_parse).
+int sst_scan_host(const ScanIn& in, const ScanOut& o, bool crc) {
+  if (int rc = sst_scan_check(in, o)) return rc;
+  const std::uint8_t* f = in.file;
+  // footer
+  if (in.size < kSstMinFile) return sst_scan_corrupted(o, TKV_SST_BAD_FOOTER, "SSTable scan: the file is shorter than an index and a footer");
+  const std::uint8_t* foot = f + (in.size - kSstFooter);
+  const std::uint32_t ioff32 = static_cast<std::uint32_t>(le_bytes(foot, 4)), isz32 = static_cast<std::uint32_t>(le_bytes(foot + 4, 4));
+  if (!sst_footer_ok(in.size, ioff32, isz32))
+    return sst_scan_corrupted(o, TKV_SST_BAD_FOOTER, "SSTable scan: the footer does not describe this file");
+  const std::uint64_t ioff = ioff32, isz = isz32;
+  if (crc) {
+    const int rc = tkv_sst_verify_footer(f + ioff, isz, foot);
+    if (rc == TKV_CORRUPTED) return sst_scan_corrupted(o, TKV_SST_BAD_FOOTER, "SSTable scan: corrupted index or footer");
+    if (rc) return rc;
+  }
+  // index
+  const std::uint8_t* idx = f + ioff;
+  const std::uint64_t B = le_bytes(idx, 8);
+  bool iok = sst_index_count_ok(B, isz);
+  std::vector<ScanBlock> blk;
+  if (iok) {
+    blk.resize(B);
+    std::uint64_t p = 8;
+    for (std::uint64_t j = 0; j < B && iok; ++j) {
+      iok = p < isz;
+      if (!iok) break;
+      const SstLink s = sst_chain_next(static_cast<std::uint32_t>(bytes_word(idx + p, isz - p, kSstLenBytes)), p, isz, kSstIndexFixed);
+      iok = s.ok;
+      if (!iok) break;
+      const std::uint8_t* e = idx + p + s.n + s.len;
+      blk[j] = ScanBlock{le_bytes(e, 8), le_bytes(e + 8, 8), ioff + p + s.n, s.len};
+      iok = sst_index_block_ok(blk[j].off, blk[j].size, ioff);
+      p = s.next;
+    }
+    iok = iok && p == isz;
+  }
+  if (!iok) return sst_scan_corrupted(o, TKV_SST_BAD_INDEX, "SSTable scan: the index framing does not hold");
+  // blocks: the checksums through tkv_sst_verify_blocks' path, the parse on host threads
+  std::uint64_t bad = B;
+  if (crc && B) {
+    std::vector<std::uint64_t> off(B), size(B);
+    for (std::uint64_t j = 0; j < B; ++j) {
+      off[j] = blk[j].off;
+      size[j] = blk[j].size;
+    }
+    std::uint64_t n_bad = 0, first_bad = B;
+    const int rc = tkv_sst_verify_blocks(f, off.data(), size.data(), B, &n_bad, &first_bad);
+    if (rc == TKV_CORRUPTED) bad = first_bad;
+    else if (rc) return rc;
+  }
+  std::vector<std::uint64_t> first(B + 1, 0);
+  {
+    std::vector<std::uint64_t> tbad(host_threads() + 1u, B);
+    parallel_ranges(B, [&](unsigned t, std::uint64_t lo, std::uint64_t hi) {
+      for (std::uint64_t j = lo; j < hi; ++j) {
+        first[j + 1] = sst_scan_block(f, blk[j], nullptr);
+        if (!first[j + 1] && tbad[t] == B) tbad[t] = j;
+      }
+    });
+    for (std::uint64_t v : tbad) bad = std::min(bad, v);
+  }
+  if (bad < B) return sst_scan_corrupted(o, bad, "SSTable scan: corrupted data block");
+  for (std::uint64_t j = 0; j < B; ++j) first[j + 1] += first[j];
+  const std::uint64_t n = first[B];
+  std::vector<ScanRec> rec(n);
+  parallel_ranges(B, [&](unsigned, std::uint64_t lo, std::uint64_t hi) {
+    for (std::uint64_t j = lo; j < hi; ++j) (void)sst_scan_block(f, blk[j], rec.data() + first[j]);
+  });
+  std::vector<std::uint64_t> ko(n + 1, 0), vo(n + 1, 0);
+  for (std::uint64_t i = 0; i < n; ++i) {
+    ko[i + 1] = ko[i] + rec[i].kl;
+    vo[i + 1] = vo[i] + rec[i].vl;
+  }
+  *o.n_entries = n;
+  *o.n_blocks = B;
+  *o.keys_size = ko[n];
+  *o.vals_size = vo[n];
+  *o.bad_block = B;
+  const bool kviews = in.flags & TKV_SST_SCAN_KEY_VIEWS, vviews = in.flags & TKV_SST_SCAN_VAL_VIEWS;
+  const bool want_entries = ptr_ok(o.key_off) || ptr_ok(o.key_len) || ptr_ok(o.val_off) || ptr_ok(o.val_len);
+  const bool want_blocks = ptr_ok(o.block_off) || ptr_ok(o.block_size) || ptr_ok(o.block_first);
+  if ((want_entries && n > o.entry_cap) || (want_blocks && B > o.block_cap) || (!kviews && ko[n] > o.keys_cap) ||
+      (!vviews && vo[n] > o.vals_cap))
+    return set_error(TKV_BUFFER_OVERFLOW, "SSTable scan: an output does not fit its cap");
+  const bool kcopy = !kviews && ptr_ok(o.keys), vcopy = !vviews && ptr_ok(o.vals);
+  for (std::uint64_t j = 0; j < B; ++j) {
+    if (ptr_ok(o.block_off)) o.block_off[j] = blk[j].off;
+    if (ptr_ok(o.block_size)) o.block_size[j] = static_cast<std::uint32_t>(blk[j].size);
+    if (ptr_ok(o.block_first)) o.block_first[j] = static_cast<std::uint32_t>(first[j]);
+  }
+  parallel_ranges(n, [&](unsigned, std::uint64_t lo, std::uint64_t hi) {
+    for (std::uint64_t i = lo; i < hi; ++i) {
+      const ScanRec& r = rec[i];
+      if (ptr_ok(o.key_len)) o.key_len[i] = r.kl;
+      if (ptr_ok(o.val_len)) o.val_len[i] = r.vl;
+      if (ptr_ok(o.key_off)) o.key_off[i] = kviews ? r.kpos : ko[i];
+      if (ptr_ok(o.val_off)) o.val_off[i] = vviews ? r.vpos : vo[i];
+      if (kcopy && r.kl) std::memcpy(o.keys + ko[i], f + r.kpos, r.kl);
+      if (vcopy && r.vl) std::memcpy(o.vals + vo[i], f + r.vpos, r.vl);
+    }
+  });
+  return TKV_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tkv_sst_scan_device(const uint8_t* d_file, uint64_t file_size, uint32_t flags, uint64_t* d_key_off, uint32_t* d_key_len,
+                        uint64_t* d_val_off, uint32_t* d_val_len, uint64_t entry_cap, uint8_t* d_keys, uint64_t keys_cap,
+                        uint8_t* d_vals, uint64_t vals_cap, uint64_t* d_block_off, uint32_t* d_block_size,
+                        uint32_t* d_block_first, uint64_t block_cap, uint64_t* n_entries, uint64_t* n_blocks,
+                        uint64_t* keys_size, uint64_t* vals_size, uint64_t* bad_block, void* stream) {
+  const ScanIn in{d_file, file_size, flags};
+  const ScanOut o{d_key_off, d_key_len, d_val_off, d_val_len, entry_cap, d_keys, keys_cap, d_vals, vals_cap, d_block_off,
+                  d_block_size, d_block_first, block_cap, n_entries, n_blocks, keys_size, vals_size, bad_block};
+  if (int rc = sst_scan_check(in, o)) return rc;
+  if (file_size < kSstMinFile) return sst_scan_corrupted(o, TKV_SST_BAD_FOOTER, "SSTable scan: the file is shorter than an index and a footer");
+  return sst_scan_device_impl(d_file, file_size, flags, d_key_off, d_key_len, d_val_off, d_val_len, entry_cap, d_keys, keys_cap,
+                              d_vals, vals_cap, d_block_off, d_block_size, d_block_first, block_cap, n_entries, n_blocks,
+                              keys_size, vals_size, bad_block, static_cast<hipStream_t>(stream));
+}
+
+int tkv_sst_scan(const uint8_t* h_file, uint64_t file_size, uint32_t flags, uint64_t* h_key_off, uint32_t* h_key_len,
+                 uint64_t* h_val_off, uint32_t* h_val_len, uint64_t entry_cap, uint8_t* h_keys, uint64_t keys_cap,
+                 uint8_t* h_vals, uint64_t vals_cap, uint64_t* h_block_off, uint32_t* h_block_size, uint32_t* h_block_first,
+                 uint64_t block_cap, uint64_t* n_entries, uint64_t* n_blocks, uint64_t* keys_size, uint64_t* vals_size,
+                 uint64_t* bad_block) {
+  const ScanIn in{h_file, file_size, flags};
+  const ScanOut o{h_key_off, h_key_len, h_val_off, h_val_len, entry_cap, h_keys, keys_cap, h_vals, vals_cap, h_block_off,
+                  h_block_size, h_block_first, block_cap, n_entries, n_blocks, keys_size, vals_size, bad_block};
+  return sst_scan_host(in, o, true);
+}
+
+int tkv_debug_sst_scan_parse(const uint8_t* h_file, uint64_t file_size, uint32_t flags, uint64_t* h_key_off,
+                             uint32_t* h_key_len, uint64_t* h_val_off, uint32_t* h_val_len, uint64_t entry_cap,
+                             uint8_t* h_keys, uint64_t keys_cap, uint8_t* h_vals, uint64_t vals_cap, uint64_t* h_block_off,
+                             uint32_t* h_block_size, uint32_t* h_block_first, uint64_t block_cap, uint64_t* n_entries,
+                             uint64_t* n_blocks, uint64_t* keys_size, uint64_t* vals_size, uint64_t* bad_block) {
+  const ScanIn in{h_file, file_size, flags};
+  const ScanOut o{h_key_off, h_key_len, h_val_off, h_val_len, entry_cap, h_keys, keys_cap, h_vals, vals_cap, h_block_off,
+                  h_block_size, h_block_first, block_cap, n_entries, n_blocks, keys_size, vals_size, bad_block};
+  return sst_scan_host(in, o, false);
+}
+
+}  // extern "C"

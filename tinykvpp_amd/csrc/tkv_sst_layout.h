@@ -1,6 +1,7 @@
 // The SSTable file image tkv_sst_build[_device] writes (include/tkv_crc32.h "SSTable flush"): the
 // arithmetic of sstable_writer::append / get_data_block / get_index / get_footer shared by the host
-// path (tkv_formats.cpp) and the device kernels (tkv_sst_build.hip). Plain C++.
+// path (tkv_formats.cpp) and the device kernels (tkv_sst_build.hip), and the checks of the reader
+// tkv_sst_scan[_device] ("SSTable scan"; tkv_formats.cpp, tkv_sst_scan.hip). Plain C++.
 #pragma once
 
 #include <cstdint>
@@ -65,6 +66,92 @@ inline std::uint32_t sst_rounds(std::uint64_t bmax) {
   std::uint32_t r = 0;
   while ((std::uint64_t(1) << r) < bmax + 1u) ++r;
   return r;
+}
+
+// ---- the reader's arithmetic (include/tkv_crc32.h "SSTable scan") -------------------
+// Shared by the host scan (tkv_formats.cpp) and the device kernels (tkv_sst_scan.hip). Nothing here
+// touches memory: a caller packs the (at most 5) bytes it may read into a word, bounded by what is left
+// of the region, and gets positions back; every sum is 64-bit.
+
+constexpr std::uint32_t kSstMinFile = 28;     // an index of 8 bytes and the footer
+constexpr std::uint32_t kSstMinIndexEntry = 17;  // varint(0) | u64 | u64
+constexpr std::uint32_t kSstMinBlock = 22;    // TKV_SST_MIN_IMAGE
+constexpr std::uint32_t kSstLenBytes = 4;     // a length's varint: what append counts for it
+constexpr std::uint32_t kSstBodyLenBytes = 5; // the body's length prefix: z fits u32
+
+// A LEB128 value whose first bytes are the little-endian bytes of w, of which avail are real: n = its
+// byte count, 0 when it does not end within min(avail, maxb) bytes (maxb <= 5). Redundant encodings
+// (80 00) are taken at their value.
+struct SstVarint {
+  std::uint64_t v;
+  std::uint32_t n;
+};
+TKV_HD inline SstVarint sst_varint_word(std::uint64_t w, std::uint64_t avail, std::uint32_t maxb) {
+  SstVarint r{0u, 0u};
+  const std::uint32_t lim = avail < maxb ? static_cast<std::uint32_t>(avail) : maxb;
+  for (std::uint32_t k = 0; k < lim; ++k) {
+    const std::uint64_t b = (w >> (8u * k)) & 0xFFu;
+    r.v |= (b & 0x7Fu) << (7u * k);
+    if (b < 0x80u) {
+      r.n = k + 1u;
+      return r;
+    }
+  }
+  r.v = 0;
+  return r;
+}
+
+// The footer's fields against the file: 28 <= file_size <= 2^32 - 1, index_offset + index_size + 20 ==
+// file_size, index_size >= 8 (sst.read_index's rules).
+TKV_HD inline bool sst_footer_ok(std::uint64_t file_size, std::uint32_t index_offset, std::uint32_t index_size) {
+  return file_size >= kSstMinFile && file_size <= 0xFFFFFFFFull && index_size >= 8u &&
+         std::uint64_t(index_offset) + index_size + kSstFooter == file_size;
+}
+TKV_HD inline bool sst_index_count_ok(std::uint64_t B, std::uint64_t index_size) {
+  return B <= (index_size - 8u) / kSstMinIndexEntry;
+}
+
+// One step of a chain of length-prefixed strings in a region of `end` bytes: the string at position p
+// (p < end) is varint(len) | len bytes | `fixed` more bytes, w holds the bytes at p (min(4, end - p) of
+// them real). ok: the varint ends within 4 bytes and the whole entry lies inside the region; then n is
+// the varint's byte count, len the length and next = p + n + len + fixed <= end.
+struct SstLink {
+  std::uint64_t next;
+  std::uint32_t len, n;
+  bool ok;
+};
+// sst_varint_word(w, avail, 4) without a loop or a branch: the walk of a block takes this step once per
+// string, all of it on the scalar unit of a wave whose lanes move together.
+TKV_HD inline SstVarint sst_varint4(std::uint32_t w, std::uint64_t avail) {
+  const std::uint32_t c0 = w & 0x80u, c1 = w & 0x8000u, c2 = w & 0x800000u, c3 = w & 0x80000000u;
+  const std::uint32_t n = !c0 ? 1u : !c1 ? 2u : !c2 ? 3u : !c3 ? 4u : 0u;
+  const std::uint32_t v = (w & 0x7Fu) | ((w >> 1) & 0x3F80u) | ((w >> 2) & 0x1FC000u) | ((w >> 3) & 0xFE00000u);
+  const bool ok = n != 0u && n <= avail;
+  const std::uint32_t bits = 7u * (ok ? n : 1u);
+  return SstVarint{ok ? v & (0xFFFFFFFFu >> (32u - bits)) : 0u, ok ? n : 0u};
+}
+
+TKV_HD inline SstLink sst_chain_next(std::uint32_t w, std::uint64_t p, std::uint64_t end, std::uint32_t fixed) {
+  const SstVarint v = sst_varint4(w, end - p);
+  SstLink s{0u, static_cast<std::uint32_t>(v.v), v.n, false};
+  if (!v.n) return s;
+  s.next = p + v.n + v.v + fixed;
+  s.ok = s.next <= end;
+  return s;
+}
+
+// An index entry's block against the data region [0, index_offset).
+TKV_HD inline bool sst_index_block_ok(std::uint64_t off, std::uint64_t size, std::uint64_t index_offset) {
+  return size >= kSstMinBlock && off <= index_offset && size <= index_offset - off;
+}
+
+// The fixed part of a data-block image of `size` bytes (size >= 22): byte 0, u32 c at 1, u32 z at 5, the
+// u32 at 9, byte 13, and the body's length prefix zv (the varint at byte 21, read with size - 21 bytes
+// available and at most 5). True: the body is the z bytes at 21 + zv.n and a walk of c entries is bounded.
+TKV_HD inline bool sst_block_header_ok(std::uint32_t b0, std::uint32_t c, std::uint32_t z, std::uint32_t z2, std::uint32_t comp,
+                                       std::uint64_t size, SstVarint zv) {
+  return b0 == 20u && z2 == z && comp == 0u && std::uint64_t(kSstOverhead) + z == size && c >= 1u &&
+         8ull * c <= z && zv.n != 0u && zv.v == z;
 }
 
 }  // namespace tkv

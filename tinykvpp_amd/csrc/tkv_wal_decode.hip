@@ -15,11 +15,10 @@
 // arena and output tile the record whose span holds the tile's first byte and the record whose span holds
 // its last byte, so no emit wave searches the offsets. Empty spans hold no byte: they write no table
 // entry, so a run of them of any length in front of, behind or across a tile edge is skipped.
-// dec_emit, per copied arena: the arena cut into tiles of kDecTile bytes, tile t, t + W, ... to wave t of
-// W. A wave builds its tile in an LDS window, two records per lane and round: spans up to kShortSpan bytes
-// by their lane, longer ones by the whole wave (tkv_wal_copy.h: lane_copy2, wave_copy), each clipped
-// to the tile, and stores the tile once (store_tile). The kernel needs no CRC tables: its LDS is the
-// windows alone.
+// span_emit (tkv_wal_emit.h, shared with the SSTable scan), per copied arena: the arena cut into tiles of
+// kDecTile bytes, tile t, t + W, ... to wave t of W. A wave builds its tile in an LDS window and stores it
+// once. WalSrc tells it where a record's key or value lies. The kernel needs no CRC tables: its LDS is
+// the windows alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,21 +30,14 @@
 #include "tkv_device_util.h"
 #include "tkv_engine.h"
 #include "tkv_wal_copy.h"
+#include "tkv_wal_emit.h"
 #include "tkv_wal_device.h"
 #include "tkv_wal_layout.h"
 
 namespace tkv {
 namespace {
 
-constexpr std::uint32_t kDecTile = 4096;             // arena bytes per emit tile
-constexpr std::uint32_t kDecWin = 16 + kDecTile;     // the tile behind its destination's offset in its first granule
-constexpr unsigned kDecWaves = 8;                    // waves per workgroup: 8 windows, 32.1 KiB of LDS
-constexpr unsigned kDecThreads = 64 * kDecWaves;
-constexpr unsigned kDecGroupsPerCu = 2;              // resident workgroups the launch is sized for
-constexpr std::uint32_t kDecSteps = (kDecWin + 1023u) / 1024u;  // wave_copy steps of a span clipped to a tile
 constexpr unsigned kDecHres = 4;                     // words of the pinned result block
-static_assert(kDecTile % 16 == 0 && kDecWin % 16 == 0, "16-byte granules");
-static_assert(kDecGroupsPerCu * kDecWaves * kDecWin <= 163840, "LDS");
 
 struct DecArgs {
   const std::uint8_t* img;
@@ -176,18 +168,6 @@ __global__ void dec_publish(const std::uint64_t* ktop, const std::uint64_t* vtop
   }
 }
 
-// Span i = arena bytes [o, o + len) of an arena of `total` bytes, len > 0: for every tile it has a byte
-// in, the tile's first record when it holds the tile's first byte and its last record when it holds the
-// tile's last byte. One writer per word: the non-empty spans tile the arena.
-__device__ __forceinline__ void tile_entries(std::uint32_t* tile, std::uint64_t i, std::uint64_t o, std::uint64_t len,
-                                             std::uint64_t total) {
-  const std::uint64_t e = o + len < total ? o + len : total;  // (o + len <= total: the scan's own sums)
-  for (std::uint64_t t = o / kDecTile; t * kDecTile < e; ++t) {
-    if (o <= t * kDecTile) tile[2u * t] = static_cast<std::uint32_t>(i);
-    if (e >= (t + 1u) * kDecTile || e == total) tile[2u * t + 1u] = static_cast<std::uint32_t>(i);
-  }
-}
-
 __global__ __launch_bounds__(kScanThreads) void dec_finish(DecArgs a, const std::uint64_t* kbase, const std::uint64_t* vbase) {
   const std::uint64_t i = blockIdx.x * static_cast<std::uint64_t>(kScanThreads) + threadIdx.x;
   if (i >= a.n) return;
@@ -214,79 +194,20 @@ __global__ __launch_bounds__(kScanThreads) void dec_finish(DecArgs a, const std:
 
 // ---- emit -------------------------------------------------------------------------------------------
 
-struct EmitArgs {
+// Where record i's span lies in the image for the shared emit (tkv_wal_emit.h): the key behind the
+// record's header, the value behind its key.
+template <bool VAL>
+struct WalSrc {
   const std::uint8_t* img;
   const std::uint64_t* off64;
   const std::uint32_t* off32;
   const std::uint64_t* kpre;   // the key spans: a value lies behind its record's key
-  const std::uint64_t* pre;    // the spans of the arena being written
-  std::uint8_t* dst;
-  std::uint64_t total;
-  const std::uint32_t* tile;
-  std::uint64_t ntiles;
-  std::uint64_t n;
-  std::uint32_t nwaves;
+  __device__ __forceinline__ std::uintptr_t operator()(std::uint64_t i) const {
+    const std::uint64_t off = off64 ? off64[i] : static_cast<std::uint64_t>(off32[i]);
+    const std::uint64_t so = off + kWalMeta + (VAL ? kpre[i + 1u] - kpre[i] : 0u);
+    return reinterpret_cast<std::uintptr_t>(img) + static_cast<std::uintptr_t>(so);
+  }
 };
-
-// Record i's span as the emit pass reads it, one record per lane: arena offset, length (the scan's:
-// a header is not read again) and source address.
-struct DecRec {
-  std::uint64_t ao;
-  std::uint64_t len;
-  std::uintptr_t src;
-};
-template <bool VAL>
-__device__ __forceinline__ DecRec load_rec(const EmitArgs& a, std::uint64_t i, bool act) {
-  DecRec r{0u, 0u, 0};
-  if (act) {
-    r.ao = a.pre[i];
-    r.len = a.pre[i + 1u] - r.ao;
-    const std::uint64_t off = a.off64 ? a.off64[i] : static_cast<std::uint64_t>(a.off32[i]);
-    const std::uint64_t so = off + kWalMeta + (VAL ? a.kpre[i + 1u] - a.kpre[i] : 0u);
-    r.src = reinterpret_cast<std::uintptr_t>(a.img) + static_cast<std::uintptr_t>(so);
-  }
-  return r;
-}
-
-template <bool VAL>
-__device__ __forceinline__ void emit_tile(const EmitArgs& a, std::uint8_t* win, std::uint64_t t, uint2 head, std::uint32_t lane) {
-  const std::uint64_t ts = t * kDecTile;
-  const std::uint64_t te = ts + kDecTile < a.total ? ts + kDecTile : a.total;
-  const std::uint64_t first = head.x, last = head.y;
-  std::uint8_t* const dst = a.dst + ts;
-  const std::uint32_t o = static_cast<std::uint32_t>(reinterpret_cast<std::uintptr_t>(dst) & 15u);  // window granules are the arena's
-  for (std::uint64_t rb = first; rb <= last; rb += 128u) {
-    const std::uint64_t i0 = rb + lane, i1 = i0 + 64u;
-    const DecRec r0 = load_rec<VAL>(a, i0, i0 <= last && i0 < a.n);
-    const DecRec r1 = load_rec<VAL>(a, i1, i1 <= last && i1 < a.n);
-    const Span s0 = clip_span(r0.src, r0.len, r0.ao, ts, te, ts, o);
-    const Span s1 = clip_span(r1.src, r1.len, r1.ao, ts, te, ts, o);
-    lane_copy2(win, lane_span(s0.d, s0.src, s0.len, s0.len != 0u && s0.len <= kShortSpan),
-               lane_span(s1.d, s1.src, s1.len, s1.len != 0u && s1.len <= kShortSpan));
-    wave_spans<kDecSteps>(win, s0, lane);
-    wave_spans<kDecSteps>(win, s1, lane);
-  }
-  wave_sync();
-  store_tile(win, dst, o, static_cast<std::uint32_t>(te - ts), lane);
-  wave_sync();
-}
-
-template <bool VAL>
-__global__ __launch_bounds__(kDecThreads) void dec_emit(EmitArgs a) {
-  __shared__ __attribute__((aligned(16))) std::uint8_t lds[kDecWaves * kDecWin];
-  const std::uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const std::uint32_t lane = threadIdx.x & 63u;
-  std::uint8_t* win = lds + wv * kDecWin;
-  std::uint64_t t = blockIdx.x * kDecWaves + wv;
-  if (t >= a.ntiles) return;
-  // a tile's first and last record are read one tile ahead
-  uint2 h = *reinterpret_cast<const uint2*>(a.tile + 2u * t);
-  for (; t < a.ntiles; t += a.nwaves) {
-    const uint2 hn = t + a.nwaves < a.ntiles ? *reinterpret_cast<const uint2*>(a.tile + 2u * (t + a.nwaves)) : make_uint2(1u, 0u);
-    emit_tile<VAL>(a, win, t, h, lane);
-    h = hn;
-  }
-}
 
 // ---- host side --------------------------------------------------------------------------------------
 
@@ -335,22 +256,14 @@ int scratch(DecScratch** out) {
 // The emit of one copied arena; returns its waves.
 template <bool VAL>
 std::uint32_t launch_emit(const DecScratch& s, const DecArgs& a, std::uint8_t* dst, std::uint64_t total, hipStream_t st) {
-  EmitArgs e{};
-  e.img = a.img;
-  e.off64 = a.off64;
-  e.off32 = a.off32;
-  e.kpre = a.kpre;
+  EmitArgs<WalSrc<VAL>> e{};
+  e.src = WalSrc<VAL>{a.img, a.off64, a.off32, a.kpre};
   e.pre = VAL ? a.vpre : a.kpre;
   e.dst = dst;
   e.total = total;
   e.tile = VAL ? a.vtile : a.ktile;
-  e.ntiles = (total + kDecTile - 1u) / kDecTile;
   e.n = a.n;
-  const std::uint64_t want = (e.ntiles + kDecWaves - 1u) / kDecWaves;
-  const unsigned grid = static_cast<unsigned>(std::min<std::uint64_t>(want, static_cast<std::uint64_t>(s.ncu) * kDecGroupsPerCu));
-  e.nwaves = grid * kDecWaves;
-  hipLaunchKernelGGL(dec_emit<VAL>, dim3(grid), dim3(kDecThreads), 0, st, e);
-  return e.nwaves;
+  return launch_span_emit(s.ncu, e, st);
 }
 
 int decode_locked(DecScratch& s, DecArgs a, std::uint8_t* d_keys, std::uint64_t keys_cap, std::uint8_t* d_vals,

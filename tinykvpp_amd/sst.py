@@ -300,3 +300,116 @@ def read_index(file):
     if pos != len(idx):
         raise ValueError("bytes left behind the last index entry")
     return out
+
+
+# ---- scan: verify, index and entries of a file image (include/tkv_crc32.h "SSTable scan") ------------
+SCAN_KEY_VIEWS = 1
+SCAN_VAL_VIEWS = 2
+BAD_FOOTER = 2**64 - 1
+BAD_INDEX = 2**64 - 2
+
+
+class SstCorrupted(ValueError):
+    """A file the scan rejects. ``bad_block`` is "footer", "index" or the number of the first bad block."""
+
+    def __init__(self, bad_block, msg):
+        self.bad_block = {BAD_FOOTER: "footer", BAD_INDEX: "index"}.get(bad_block, bad_block)
+        super().__init__(f"corrupted SSTable ({self.bad_block}): {msg}")
+
+
+class ScannedTable:
+    """What scan_device / scan return: the entries as ``keys`` / ``key_off`` / ``key_len`` and ``vals`` /
+    ``val_off`` / ``val_len`` (the columns build_device takes; with a views flag the arena is the file
+    image itself) and the data blocks' ``block_off`` / ``block_size`` / ``block_first``."""
+
+    __slots__ = ("keys", "key_off", "key_len", "vals", "val_off", "val_len", "block_off", "block_size", "block_first",
+                 "n_entries", "n_blocks")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def entries(self):
+        """[(key, value)] as bytes (tests and small tables)."""
+        def host(t):
+            return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+        keys, vals = host(self.keys).view(np.uint8).tobytes(), host(self.vals).view(np.uint8).tobytes()
+        ko, vo = host(self.key_off).view(np.uint64), host(self.val_off).view(np.uint64)
+        kl, vl = host(self.key_len).view(np.uint32), host(self.val_len).view(np.uint32)
+        return [(keys[int(ko[i]):int(ko[i]) + int(kl[i])], vals[int(vo[i]):int(vo[i]) + int(vl[i])])
+                for i in range(self.n_entries)]
+
+
+def _scan(fn, file_ptr, size, flags, alloc, ptr, file_arena, tail):
+    """The sizing call, then the scan into freshly allocated arrays. ``alloc(count, kind)`` makes an array
+    (kind "u8" / "u64" / "u32"), ``ptr`` its address, ``tail`` the trailing arguments (the stream)."""
+    from ._lib import BUFFER_OVERFLOW
+    out = [ctypes.c_uint64(0) for _ in range(5)]  # n_entries, n_blocks, keys_size, vals_size, bad_block
+    refs = [ctypes.byref(s) for s in out]
+
+    def done(rc):
+        if rc == CORRUPTED:
+            raise SstCorrupted(out[4].value, load_library().tkv_last_error().decode(errors="replace"))
+        return rc
+    rc = done(fn(file_ptr, size, flags, None, None, None, None, 0, None, 0, None, 0, None, None, None, 0, *refs, *tail))
+    if rc not in (OK, BUFFER_OVERFLOW):
+        check(rc)
+    n, nb, ks, vs = (s.value for s in out[:4])
+    kviews, vviews = bool(flags & SCAN_KEY_VIEWS), bool(flags & SCAN_VAL_VIEWS)
+    koff, klen, voff, vlen = alloc(n, "u64"), alloc(n, "u32"), alloc(n, "u64"), alloc(n, "u32")
+    keys = file_arena if kviews else alloc(ks, "u8")
+    vals = file_arena if vviews else alloc(vs, "u8")
+    boff, bsize, bfirst = alloc(nb, "u64"), alloc(nb, "u32"), alloc(nb, "u32")
+    check(done(fn(file_ptr, size, flags, ptr(koff), ptr(klen), ptr(voff), ptr(vlen), n,
+                  None if kviews else ptr(keys), ks, None if vviews else ptr(vals), vs,
+                  ptr(boff), ptr(bsize), ptr(bfirst), nb, *refs, *tail)))
+    return ScannedTable(keys=keys, key_off=koff, key_len=klen, vals=vals, val_off=voff, val_len=vlen, block_off=boff,
+                        block_size=bsize, block_first=bfirst, n_entries=n, n_blocks=nb)
+
+
+def scan_device(file, key_views=False, val_views=False, stream=None):
+    """Verify a file image held on the device (a uint8 CUDA tensor of any alignment) and take it apart
+    (tkv_sst_scan_device): makes the sizing call, then the scan. Returns a ScannedTable of CUDA tensors in
+    the dtypes build_device takes: keys / vals uint8, key_off / val_off / block_off int64, key_len /
+    val_len / block_size / block_first int32 (u32 values). With ``key_views`` / ``val_views`` nothing is
+    copied for that arena: ``keys`` / ``vals`` is ``file`` and the offsets point into it. A corrupted file
+    raises SstCorrupted. Synchronous on ``stream``."""
+    import torch
+    from .crc32 import _launch_stream
+    if not isinstance(file, torch.Tensor) or file.dtype != torch.uint8 or not file.is_cuda or file.dim() != 1 or \
+            not file.is_contiguous():
+        raise ValueError("file must be a contiguous 1-D uint8 CUDA tensor")
+    dev = file.device
+    other = stream is not None and stream != torch.cuda.current_stream(dev)
+    kinds = {"u8": torch.uint8, "u64": torch.int64, "u32": torch.int32}
+
+    def alloc(count, kind):
+        # (an arena without a byte is returned as one spare byte: it still has an address, which
+        # build_device requires)
+        t = torch.empty(max(count, 1), dtype=kinds[kind], device=dev)
+        if count or kind != "u8":
+            t = t[:count]
+        if other:
+            t.record_stream(stream)
+        return t
+    flags = (SCAN_KEY_VIEWS if key_views else 0) | (SCAN_VAL_VIEWS if val_views else 0)
+    return _scan(load_library().tkv_sst_scan_device, ctypes.c_void_p(file.data_ptr()) if file.numel() else None,
+                 file.numel(), flags, alloc, lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None, file,
+                 (_launch_stream(stream, dev),))
+
+
+def scan(file, key_views=False, val_views=False):
+    """The same on the host (tkv_sst_scan): ``file`` is bytes or a uint8 numpy array; the parse and the
+    copies run on host threads, the checksums on the GPU. Returns a ScannedTable of numpy arrays (uint8,
+    uint64 offsets, uint32 lengths)."""
+    if isinstance(file, np.ndarray):
+        if file.dtype != np.uint8 or file.ndim != 1:
+            raise ValueError("file must be a 1-D uint8 numpy array")
+        buf = np.ascontiguousarray(file)
+    else:
+        buf = np.frombuffer(bytes(file), np.uint8)
+    kinds = {"u8": np.uint8, "u64": np.uint64, "u32": np.uint32}
+    flags = (SCAN_KEY_VIEWS if key_views else 0) | (SCAN_VAL_VIEWS if val_views else 0)
+    return _scan(load_library().tkv_sst_scan, ctypes.c_void_p(buf.ctypes.data) if buf.size else None, buf.size, flags,
+                 lambda count, kind: np.empty(count, kinds[kind]),
+                 lambda a: ctypes.c_void_p(a.ctypes.data) if a.size else None, buf, ())
