@@ -515,6 +515,74 @@ int tkv_sst_scan(const uint8_t *h_file, uint64_t file_size, uint32_t flags,
                  uint64_t *n_entries, uint64_t *n_blocks, uint64_t *keys_size, uint64_t *vals_size,
                  uint64_t *bad_block);
 
+/* ---- Memtable replay: sort and dedupe a decoded WAL batch ------------------------- */
+
+/* What a memtable holds after engine::create's replay loop (engine.cpp:30-47) has inserted a whole batch
+ * (memtable.cpp:58-72, skiplist.hpp:201-242), in iteration order, for n records given in log order as the
+ * columns tkv_wal_decode_device writes: user key K_i = [keys + key_off[i], + key_len[i]), value span
+ * (val_off[i], val_len[i]), op[i], tomb[i], seq[i]. The outputs are valid inputs of tkv_sst_build_device.
+ * Order: internal_key_comparator compares user keys only, through simd_comparator: unsigned bytewise, and
+ * when one key is a prefix of the other the shorter is smaller ("" < "a" < "a\0" < "a\0\0" < "a\1" <
+ * "\x80"). seq, tomb and op do not take part.
+ * Replacement: skiplist::insert of an equal user key replaces the node, so of all records with one user
+ * key the one LATEST IN INPUT ORDER survives, whatever its seq.
+ * Operation: op == 0 (put) keeps the record's value span; op == 1 (del) stores an empty value (val_len 0,
+ * val_off as the record's), whatever the record carried; any other op is the reference's FR_VERIFY abort:
+ * TKV_CORRUPTED, *first_bad = the smallest such index, nothing written to any output array, *n_entries =
+ * *ikeys_size = 0. tomb is taken from the record for both ops. Otherwise *first_bad = n.
+ * Internal key (encode_internal_key, sstable_format.cpp:9-25): user_key | u64 seq LE | u64 timestamp LE |
+ * u8 tombstone, 17 bytes behind the key. The tombstone byte is tomb[i] != 0. The reference's timestamp is
+ * wall_clock_ms() at each put and cannot be reproduced: timestamp_ms goes into every internal key.
+ * Inputs: val_off, val_len, op, tomb, seq are nullable (value spans (0, 0); every record a put; 0; 0).
+ * VALUES ARE NEVER READ: there is no value arena among the arguments, and out_val_off / out_val_len are
+ * spans in the arena the caller holds and passes on to tkv_sst_build_device as is. Key sources may have
+ * any alignment, may overlap and may have gaps (the WAL image itself under TKV_WAL_DECODE_KEY_VIEWS); no
+ * byte outside [keys, keys + keys_size) is read for any input, beyond the aligned 16-byte granule that
+ * holds a key byte (the span copies of the WAL calls read the same way).
+ * Outputs, each nullable and then skipped: m = *n_entries distinct keys, entry j the j-th smallest;
+ * ikey_len[j] = key_len + 17, ikey_off[j] the exclusive u64 prefix sum of ikey_len, *ikeys_size the total;
+ * the internal keys back to back in d_ikeys (any byte alignment; nothing outside [d_ikeys, d_ikeys +
+ * *ikeys_size) is written or read-modify-written); out_val_off / out_val_len as above; src[j] = the index
+ * of the surviving record. The result is unique (the sort is stable), so two calls agree byte for byte.
+ * Sizing and overflow: m > entry_cap with any entry column non-NULL, or *ikeys_size > ikeys_cap with
+ * d_ikeys non-NULL: TKV_BUFFER_OVERFLOW with both sizes set and nothing written (caps of 0 with NULL
+ * arrays is the sizing call, TKV_OK).
+ * TKV_INVALID_ARGUMENT, before any device work and with no output touched: n > 2^32 - 1; NULL n_entries /
+ * ikeys_size / first_bad; with n > 0 NULL key_off / key_len, NULL keys with keys_size > 0, val_len without
+ * val_off. Found by the check pass, again with no output touched and before an op is judged: some
+ * key_off[i] + key_len[i] > keys_size; some key_len[i] + 17 >= 2^28 (the flush would refuse the entry).
+ * More than 2^31 - 1 entries can be sized and listed but not written to d_ikeys.
+ * n == 0: TKV_OK, sizes 0, *first_bad = 0, nothing else touched.
+ * The device call is synchronous on `stream` (one host synchronisation per refinement round: at most
+ * ceil(max key_len / 8) + 1 rounds, each over the still unresolved records only); with no usable GPU it
+ * returns TKV_IO_ERROR; a scratch allocation that fails returns TKV_OUT_OF_MEMORY (the scratch holds 64
+ * bytes per record, 40 more per entry when d_ikeys is written, 8 per 4 KiB of internal keys and 0.5 per
+ * record for the histograms). No key byte crosses PCIe: only a small pinned result block does. */
+int tkv_memtable_build_device(const uint8_t *d_keys, uint64_t keys_size,
+                              const uint64_t *d_key_off, const uint32_t *d_key_len,
+                              const uint64_t *d_val_off, const uint32_t *d_val_len,
+                              const uint8_t *d_op, const uint8_t *d_tomb, const uint64_t *d_seq,
+                              uint64_t n, uint64_t timestamp_ms,
+                              uint8_t *d_ikeys, uint64_t ikeys_cap,
+                              uint64_t *d_ikey_off, uint32_t *d_ikey_len,
+                              uint64_t *d_out_val_off, uint32_t *d_out_val_len, uint32_t *d_src,
+                              uint64_t entry_cap,
+                              uint64_t *n_entries, uint64_t *ikeys_size, uint64_t *first_bad, void *stream);
+
+/* The same contract with every pointer in HOST memory: a stable sort of record indices with a full-key
+ * comparator on host threads (chunk sorts, then pairwise merges), then the same dedupe and emit. It uses
+ * no GPU at all and is NOT a fallback of the device call. */
+int tkv_memtable_build(const uint8_t *h_keys, uint64_t keys_size,
+                       const uint64_t *h_key_off, const uint32_t *h_key_len,
+                       const uint64_t *h_val_off, const uint32_t *h_val_len,
+                       const uint8_t *h_op, const uint8_t *h_tomb, const uint64_t *h_seq,
+                       uint64_t n, uint64_t timestamp_ms,
+                       uint8_t *h_ikeys, uint64_t ikeys_cap,
+                       uint64_t *h_ikey_off, uint32_t *h_ikey_len,
+                       uint64_t *h_out_val_off, uint32_t *h_out_val_len, uint32_t *h_src,
+                       uint64_t entry_cap,
+                       uint64_t *n_entries, uint64_t *ikeys_size, uint64_t *first_bad);
+
 /* ---- CRC-32C (Castagnoli) — SURVEY.md §8f rank 4 ------------------------------------------------ */
 
 /* Same engine and kernels with the tables of the Castagnoli polynomial (reflected 0x82F63B78,
@@ -723,6 +791,24 @@ void tkv_debug_sst_scan_last(uint64_t out[4]);
  * out_ms[3] = emit (length scans, columns, arena gathers). Switch and return value as
  * tkv_debug_sst_build_phases. */
 int tkv_debug_sst_scan_phases(int enable, double out_ms[4]);
+
+/* Geometry of tkv_memtable_build_device: out[0] = entries per workgroup of a radix pass, out[1] = buckets
+ * of a pass, out[2] = passes a round runs at most (4 digit bits, 8 word bytes, 4 segment bytes; a pass
+ * whose bits are the same in every entry is skipped), out[3] = internal-key bytes per emit tile. A list
+ * of up to out[0] entries is sorted by one workgroup per pass, a longer one by histogram, scan and
+ * scatter. */
+void tkv_debug_memtable_geom(uint64_t out[4]);
+/* What the calling thread's last tkv_memtable_build_device did: out[0] = survivors, out[1] = refinement
+ * rounds run (the first sort included), out[2] = records that entered the second round (longer than 8
+ * bytes and equal in their first 8 to another such record), out[3] = scratch bytes the call asked for
+ * (all 0 when it did not reach its end). */
+void tkv_debug_memtable_last(uint64_t out[4]);
+/* Phase times of the calling thread's last tkv_memtable_build_device that returned TKV_OK, in
+ * milliseconds between device events on its stream: out_ms[0] = the check and the first round, out_ms[1]
+ * = the later rounds, out_ms[2] = dedupe (the survivor scans), out_ms[3] = emit (columns, metadata, the
+ * arena; with the host's read of the sizes in front). Switch and return value as
+ * tkv_debug_sst_build_phases. */
+int tkv_debug_memtable_phases(int enable, double out_ms[4]);
 
 #ifdef __cplusplus
 }

@@ -61,4 +61,34 @@ int sst_scan_device_impl(const std::uint8_t* d_file, std::uint64_t file_size, st
                          std::uint64_t block_cap, std::uint64_t* n_entries, std::uint64_t* n_blocks, std::uint64_t* keys_size,
                          std::uint64_t* vals_size, std::uint64_t* bad_block, hipStream_t st);
 
+// The arguments of tkv_memtable_build[_device] (include/tkv_crc32.h "Memtable replay").
+struct MemtableCall {
+  const std::uint8_t* keys;
+  std::uint64_t keys_size;
+  const std::uint64_t* key_off;
+  const std::uint32_t* key_len;
+  const std::uint64_t* val_off;
+  const std::uint32_t* val_len;
+  const std::uint8_t* op;
+  const std::uint8_t* tomb;
+  const std::uint64_t* seq;
+  std::uint64_t n, timestamp_ms;
+  std::uint8_t* ikeys;
+  std::uint64_t ikeys_cap;
+  std::uint64_t* ikey_off;
+  std::uint32_t* ikey_len;
+  std::uint64_t* out_val_off;
+  std::uint32_t* out_val_len;
+  std::uint32_t* src;
+  std::uint64_t entry_cap;
+  std::uint64_t *n_entries, *ikeys_size, *first_bad;
+};
+
+// tkv_memtable.hip: the memtable replay on `st` (synchronous): the checks and first comparison words,
+// rounds of a stable LSD radix sort over the unresolved records, the dedupe scans, the host's corrupted /
+// invalid / overflow decision from a pinned result, the columns and the tile emit of the internal keys.
+// Arguments and results are tkv_memtable_build_device's (1 <= n <= 2^32 - 1 and the required pointers
+// checked by the caller).
+int memtable_build_device_impl(const MemtableCall& c, hipStream_t st);
+
 }  // namespace tkv

@@ -17,6 +17,7 @@
 #include "tkv_crc32.h"
 #include "tkv_device_util.h"
 #include "tkv_engine.h"
+#include "tkv_memtable_layout.h"
 #include "tkv_sst_layout.h"
 #include "tkv_wal_device.h"
 #include "tkv_wal_layout.h"
@@ -1308,6 +1309,142 @@ int tkv_debug_sst_scan_parse(const uint8_t* h_file, uint64_t file_size, uint32_t
   const ScanOut o{h_key_off, h_key_len, h_val_off, h_val_len, entry_cap, h_keys, keys_cap, h_vals, vals_cap, h_block_off,
                   h_block_size, h_block_first, block_cap, n_entries, n_blocks, keys_size, vals_size, bad_block};
   return sst_scan_host(in, o, false);
+}
+
+}  // extern "C"
+
+namespace {
+// ---- memtable replay (engine::create's replay loop into a memtable; include/tkv_crc32.h "Memtable replay") ----
+
+// The checks both entry points make before any work.
+int memtable_check(const MemtableCall& c) {
+  if (!ptr_ok(c.n_entries) || !ptr_ok(c.ikeys_size) || !ptr_ok(c.first_bad)) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  if (c.n > 0xFFFFFFFFull) return set_error(TKV_INVALID_ARGUMENT, "memtable build: more than 2^32 - 1 records");
+  if (c.n && (!ptr_ok(c.key_off) || !ptr_ok(c.key_len) || (c.keys_size && !ptr_ok(c.keys)) ||
+              (ptr_ok(c.val_len) && !ptr_ok(c.val_off))))
+    return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  return TKV_OK;
+}
+
+// idx sorted by less, equal elements left in their order: chunks on host threads, then pairwise merges.
+template <class Less>
+void parallel_stable_sort(std::vector<std::uint32_t>& idx, Less less) {
+  const std::uint64_t n = idx.size();
+  const unsigned nt = n >= (1u << 14) ? host_threads() : 1u;
+  if (nt == 1) {
+    std::stable_sort(idx.begin(), idx.end(), less);
+    return;
+  }
+  std::vector<std::uint64_t> cut(nt + 1);
+  for (unsigned t = 0; t <= nt; ++t) cut[t] = n * t / nt;
+  {
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < nt; ++t)
+      th.emplace_back([&, t] { std::stable_sort(idx.begin() + cut[t], idx.begin() + cut[t + 1], less); });
+    for (auto& t : th) t.join();
+  }
+  for (unsigned w = 1; w < nt; w *= 2) {
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t + w < nt; t += 2 * w)
+      th.emplace_back([&, t, w] {
+        std::inplace_merge(idx.begin() + cut[t], idx.begin() + cut[t + w], idx.begin() + cut[std::min(t + 2 * w, nt)], less);
+      });
+    for (auto& t : th) t.join();
+  }
+}
+
+int memtable_build_host(const MemtableCall& c) {
+  if (int rc = memtable_check(c)) return rc;
+  const std::uint64_t n = c.n;
+  if (n == 0) {
+    *c.n_entries = *c.ikeys_size = *c.first_bad = 0;
+    return TKV_OK;
+  }
+  std::uint64_t bad = n;
+  for (std::uint64_t i = 0; i < n; ++i) {
+    const std::uint64_t ko = c.key_off[i];
+    const std::uint32_t kl = c.key_len[i];
+    if (ko > c.keys_size || kl > c.keys_size - ko) return set_error(TKV_INVALID_ARGUMENT, "memtable build: a key reaches past keys_size");
+    if (kl >= kMtMaxIkey - kMtMeta) return set_error(TKV_INVALID_ARGUMENT, "memtable build: an internal key would be 2^28 bytes or more");
+    if (bad == n && ptr_ok(c.op) && c.op[i] > kMtOpDel) bad = i;
+  }
+  *c.n_entries = 0;
+  *c.ikeys_size = 0;
+  *c.first_bad = bad;
+  if (bad < n) return set_error(TKV_CORRUPTED, "memtable build: a record's operation is neither put nor delete");
+  // simd_comparator's order: unsigned bytes, a prefix first
+  auto cmp = [&](std::uint32_t x, std::uint32_t y) {
+    const std::uint32_t lx = c.key_len[x], ly = c.key_len[y];
+    const std::uint32_t m = std::min(lx, ly);
+    const int r = m ? std::memcmp(c.keys + c.key_off[x], c.keys + c.key_off[y], m) : 0;
+    return r ? r : (lx < ly ? -1 : lx > ly ? 1 : 0);
+  };
+  std::vector<std::uint32_t> idx(n);
+  for (std::uint64_t i = 0; i < n; ++i) idx[i] = static_cast<std::uint32_t>(i);
+  parallel_stable_sort(idx, [&](std::uint32_t x, std::uint32_t y) { return cmp(x, y) < 0; });
+  // the last of every run of equal keys
+  std::vector<std::uint32_t> sv;
+  std::vector<std::uint64_t> off;
+  std::uint64_t total = 0;
+  for (std::uint64_t j = 0; j < n; ++j) {
+    if (j + 1 < n && cmp(idx[j], idx[j + 1]) == 0) continue;
+    sv.push_back(idx[j]);
+    off.push_back(total);
+    total += static_cast<std::uint64_t>(c.key_len[idx[j]]) + kMtMeta;
+  }
+  const std::uint64_t m = sv.size();
+  *c.n_entries = m;
+  *c.ikeys_size = total;
+  const bool want_cols = ptr_ok(c.ikey_off) || ptr_ok(c.ikey_len) || ptr_ok(c.out_val_off) || ptr_ok(c.out_val_len) || ptr_ok(c.src);
+  if ((want_cols && m > c.entry_cap) || (ptr_ok(c.ikeys) && total > c.ikeys_cap))
+    return set_error(TKV_BUFFER_OVERFLOW, "memtable build: the entries or the internal keys do not fit");
+  parallel_for(m, [&](std::uint64_t e) {
+    const std::uint32_t r = sv[e];
+    const std::uint32_t kl = c.key_len[r];
+    const bool del = ptr_ok(c.op) && c.op[r] == kMtOpDel;
+    if (ptr_ok(c.ikey_off)) c.ikey_off[e] = off[e];
+    if (ptr_ok(c.ikey_len)) c.ikey_len[e] = kl + kMtMeta;
+    if (ptr_ok(c.out_val_off)) c.out_val_off[e] = ptr_ok(c.val_off) ? c.val_off[r] : 0u;
+    if (ptr_ok(c.out_val_len)) c.out_val_len[e] = (del || !ptr_ok(c.val_len)) ? 0u : c.val_len[r];
+    if (ptr_ok(c.src)) c.src[e] = r;
+    if (ptr_ok(c.ikeys)) {
+      std::uint8_t* d = c.ikeys + off[e];
+      if (kl) std::memcpy(d, c.keys + c.key_off[r], kl);
+      mt_put_meta(d + kl, ptr_ok(c.seq) ? c.seq[r] : 0u, c.timestamp_ms, ptr_ok(c.tomb) ? c.tomb[r] : std::uint8_t{0});
+    }
+  });
+  return TKV_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tkv_memtable_build_device(const uint8_t* d_keys, uint64_t keys_size, const uint64_t* d_key_off, const uint32_t* d_key_len,
+                              const uint64_t* d_val_off, const uint32_t* d_val_len, const uint8_t* d_op, const uint8_t* d_tomb,
+                              const uint64_t* d_seq, uint64_t n, uint64_t timestamp_ms, uint8_t* d_ikeys, uint64_t ikeys_cap,
+                              uint64_t* d_ikey_off, uint32_t* d_ikey_len, uint64_t* d_out_val_off, uint32_t* d_out_val_len,
+                              uint32_t* d_src, uint64_t entry_cap, uint64_t* n_entries, uint64_t* ikeys_size,
+                              uint64_t* first_bad, void* stream) {
+  const MemtableCall c{d_keys, keys_size, d_key_off, d_key_len, d_val_off, d_val_len, d_op, d_tomb, d_seq, n, timestamp_ms,
+                       d_ikeys, ikeys_cap, d_ikey_off, d_ikey_len, d_out_val_off, d_out_val_len, d_src, entry_cap,
+                       n_entries, ikeys_size, first_bad};
+  if (int rc = memtable_check(c)) return rc;
+  if (n == 0) {
+    *n_entries = *ikeys_size = *first_bad = 0;
+    return TKV_OK;
+  }
+  return memtable_build_device_impl(c, static_cast<hipStream_t>(stream));
+}
+
+int tkv_memtable_build(const uint8_t* h_keys, uint64_t keys_size, const uint64_t* h_key_off, const uint32_t* h_key_len,
+                       const uint64_t* h_val_off, const uint32_t* h_val_len, const uint8_t* h_op, const uint8_t* h_tomb,
+                       const uint64_t* h_seq, uint64_t n, uint64_t timestamp_ms, uint8_t* h_ikeys, uint64_t ikeys_cap,
+                       uint64_t* h_ikey_off, uint32_t* h_ikey_len, uint64_t* h_out_val_off, uint32_t* h_out_val_len,
+                       uint32_t* h_src, uint64_t entry_cap, uint64_t* n_entries, uint64_t* ikeys_size, uint64_t* first_bad) {
+  const MemtableCall c{h_keys, keys_size, h_key_off, h_key_len, h_val_off, h_val_len, h_op, h_tomb, h_seq, n, timestamp_ms,
+                       h_ikeys, ikeys_cap, h_ikey_off, h_ikey_len, h_out_val_off, h_out_val_len, h_src, entry_cap,
+                       n_entries, ikeys_size, first_bad};
+  return memtable_build_host(c);
 }
 
 }  // extern "C"
