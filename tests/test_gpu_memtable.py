@@ -264,6 +264,58 @@ def test_recover_replay_flush(gpu, lib, oracle):
     assert [v for _, v in scanned.entries()] == [v for _, v in want]
 
 
+def test_format_scratch_grows_and_is_reused(gpu, lib, oracle):
+    """The five format paths keep per-device scratch between calls, grown by doubling through one shared
+    piece of code. In one process on one device: encode -> decode -> memtable build -> flush -> scan on 3
+    records, on 1025 (one more than a scan block: every array regrows and every scan takes a second level),
+    and on the 3 again in the grown scratch. Every stage against its sequential oracle, every time."""
+    import sst_scan_util as su
+    import wal_decode_util as wd
+    from wal_encode_util import DeviceBatch, expected, make_batch
+
+    rng = np.random.default_rng(2027)
+
+    def case(n):
+        b = make_batch(rng, rng.integers(8, 24, n), rng.integers(0, 41, n))  # random keys of 8+ bytes: distinct
+        b["op"] = rng.integers(0, 2, n, dtype=np.uint8)
+        return b, DeviceBatch(b, gpu).t, expected(b, oracle)
+
+    small, large = case(3), case(1025)
+    for b, t, (img, offs, crc) in (small, large, small):
+        n = b["n"]
+        image, rec_off, c = wal.encode_device(t["keys"], t["key_off"], t["key_len"], t["vals"], t["val_off"], t["val_len"],
+                                              t["op"], t["tomb"], t["seq"])
+        assert np.array_equal(image.cpu().numpy(), img)
+        assert np.array_equal(rec_off.cpu().numpy().view(np.uint64), offs)
+        assert np.array_equal(c.cpu().numpy().view(np.uint32), crc)
+
+        batch = wal.decode_device(image, rec_off)
+        dec = wd.expected(img, offs)
+        wd.compare({k: getattr(batch, k).cpu().numpy().view(wd.DTYPES[k]) for k in wd.COLS}, batch.keys.cpu().numpy(),
+                   batch.vals.cpu().numpy(), dec)
+
+        run = memtable.build_device(batch, timestamp_ms=n)
+        exp = mu.oracle(mu.Columns(dec["keys"], dec["key_off"], dec["key_len"], dec["val_off"], dec["val_len"], dec["op"],
+                                   dec["tomb"], dec["seq"]), n)
+        assert exp.src.size == n == last(lib)[0]
+        assert run.ikeys.cpu().numpy().tobytes() == exp.ikeys
+        assert np.array_equal(run.src.cpu().numpy().view(np.uint32), exp.src)
+        want = mu.entries(exp, dec["vals"].tobytes())
+        assert run.entries() == want
+
+        table = run.flush()
+        file_bytes, blocks, _, _ = oracle_file(want, 4096)
+        assert table.file.cpu().numpy().tobytes() == file_bytes
+        assert table.block_off.cpu().tolist() == [x[0] for x in blocks]
+
+        scanned = sst.scan_device(table.file)
+        status, _, ents, sblocks = su.oracle_scan(file_bytes)
+        assert status == "ok" and ents == want
+        assert scanned.entries() == ents
+        assert [list(x) for x in zip(scanned.block_off.cpu().tolist(), scanned.block_size.cpu().numpy().view(np.uint32).tolist(),
+                                     scanned.block_first.cpu().numpy().view(np.uint32).tolist())] == [list(x) for x in sblocks]
+
+
 # ---- threads --------------------------------------------------------------------------------------------
 
 def test_four_threads_build_at_once(gpu, lib):

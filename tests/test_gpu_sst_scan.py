@@ -112,6 +112,24 @@ def test_round_trip_fuzz(gpu, seed):
     round_trip(gpu, entries, target, misalign=seed % 16)
 
 
+def test_phase_times_only_when_enabled(gpu, lib):
+    """tkv_debug_sst_scan_phases: four phase times of this thread's last scan while enabled, zeros after a
+    scan with the timing off. Copied arenas and every output: each phase (open and index, checksum, parse,
+    emit) holds a launch."""
+    entries, target = fuzz_case(3)
+    file_bytes = oracle_file(entries, target)[0]
+    want = su.oracle_scan(file_bytes)
+    ms = (ctypes.c_double * 4)()
+    assert lib.tkv_debug_sst_scan_phases(1, None) == 0
+    try:
+        check_scan(gpu, file_bytes, want=want)
+        assert lib.tkv_debug_sst_scan_phases(1, ms) == 1 and all(v > 0 for v in ms), list(ms)
+    finally:
+        lib.tkv_debug_sst_scan_phases(0, None)
+    check_scan(gpu, file_bytes, want=want)
+    assert lib.tkv_debug_sst_scan_phases(0, ms) == 0 and list(ms) == [0, 0, 0, 0]
+
+
 # ---- the parse window -------------------------------------------------------------------------------------
 
 def test_geometry(lib):

@@ -1,5 +1,6 @@
 // Host-side launch and scratch plumbing shared by the .hip files: the HIP error return, grid
-// arithmetic, growing device arrays and the per-device scratch slot.
+// arithmetic, growing device arrays, the per-device scratch slot and its base (pinned result block,
+// device words, the wait for a tagged result) and the phase clock of the tkv_debug_*_phases hooks.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -42,6 +43,92 @@ inline int grow(void** p, std::uint64_t* cap, std::uint64_t want, std::uint64_t 
   return TKV_OK;
 }
 
+// A device array that grows by doubling and is freed with its owner.
+struct DeviceBuf {
+  void* p = nullptr;
+  std::uint64_t cap = 0;  // in units of the T it was last taken as
+  DeviceBuf() = default;
+  DeviceBuf(const DeviceBuf&) = delete;
+  DeviceBuf& operator=(const DeviceBuf&) = delete;
+  ~DeviceBuf() { (void)hipFree(p); }
+  // At least `want` T (contents dropped when it grows); a failed allocation returns grow's code.
+  template <class T>
+  int take(std::uint64_t want, T** out) {
+    if (int rc = grow(&p, &cap, want, sizeof(T))) return rc;
+    *out = static_cast<T*>(p);
+    return TKV_OK;
+  }
+};
+
+// What every per-device scratch struct starts with (the DeviceBuf members are the deriving struct's):
+// the lock of a call in progress, the pinned block a publish kernel writes results and a tag to, and a
+// few device words (flags, counters) under the name the deriving struct gives them.
+struct ScratchBase {
+  std::mutex mu;
+  int ncu = 0;
+  std::uint64_t* h_res = nullptr;       // pinned, host_words words
+  std::uint64_t* d_hres = nullptr;      // device view of h_res
+  unsigned long long* words = nullptr;  // dev_words device words
+  bool ready = false;
+  ScratchBase() = default;
+  ScratchBase(const ScratchBase&) = delete;
+  ScratchBase& operator=(const ScratchBase&) = delete;
+  ~ScratchBase() {
+    (void)hipFree(words);
+    (void)hipHostFree(h_res);
+  }
+  // Under mu, before every use: allocates what is still missing, so a call that failed half way leaks
+  // nothing and the next one completes it. need_cus: a device that reports no compute unit is an error
+  // (else the caller clamps ncu).
+  int init(std::uint64_t host_words, std::uint64_t dev_words, bool need_cus) {
+    if (ready) return TKV_OK;
+    ncu = device_cu_count();
+    if (need_cus && ncu <= 0) return set_error(TKV_IO_ERROR, "no device");
+    if (!h_res) TKV_HIP_RC(hipHostMalloc(reinterpret_cast<void**>(&h_res), host_words * sizeof(std::uint64_t), hipHostMallocDefault));
+    if (!d_hres) TKV_HIP_RC(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_hres), h_res, 0));
+    if (!words) TKV_HIP_RC(hipMalloc(reinterpret_cast<void**>(&words), dev_words * sizeof(unsigned long long)));
+    ready = true;
+    return TKV_OK;
+  }
+  // After the launches up to a publish kernel: their launch errors, the stream's end, and the tag the
+  // publish kernel left in h_res[idx] (anything else: `msg` as TKV_IO_ERROR).
+  int wait(hipStream_t st, int idx, std::uint64_t tag, const char* msg) const {
+    TKV_HIP_RC(hipGetLastError());
+    TKV_HIP_RC(hipStreamSynchronize(st));
+    if (h_res[idx] != tag) return set_error(TKV_IO_ERROR, msg);
+    return TKV_OK;
+  }
+};
+
+// Device events at the five boundaries of a call's four phases while `enable` is set; finish() leaves
+// the phase times in ms[4] (zeros when disabled or an event failed).
+struct PhaseClock {
+  hipEvent_t e[5] = {};
+  bool on = false;
+  hipStream_t st;
+  double* ms;
+  PhaseClock(hipStream_t s, bool enable, double* out_ms) : st(s), ms(out_ms) {
+    if (!enable) return;
+    on = true;
+    for (auto& x : e) on = on && hipEventCreate(&x) == hipSuccess;
+  }
+  PhaseClock(const PhaseClock&) = delete;
+  PhaseClock& operator=(const PhaseClock&) = delete;
+  void mark(int k) {
+    if (on) (void)hipEventRecord(e[k], st);
+  }
+  void finish() {  // after the stream has been synchronised
+    for (int k = 0; k < 4; ++k) {
+      float t = 0;
+      ms[k] = on && hipEventElapsedTime(&t, e[k], e[k + 1]) == hipSuccess ? t : 0.0;
+    }
+  }
+  ~PhaseClock() {
+    for (auto& x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+
 // The calling thread's device's T, created on first use and kept for the process's lifetime. T's own
 // one-time initialisation stays with the caller, under T's own mutex.
 template <class T>
@@ -54,6 +141,17 @@ int per_device(T** out) {
   std::lock_guard<std::mutex> lk(mu);
   if (!slot[dev]) slot[dev] = new T();
   *out = slot[dev];
+  return TKV_OK;
+}
+
+// The same for a T that derives from ScratchBase, initialised (ScratchBase::init).
+template <class T>
+int per_device_scratch(T** out, std::uint64_t host_words, std::uint64_t dev_words, bool need_cus) {
+  T* sp = nullptr;
+  if (int rc = per_device(&sp)) return rc;
+  std::lock_guard<std::mutex> lk(sp->mu);
+  if (int rc = sp->init(host_words, dev_words, need_cus)) return rc;
+  *out = sp;
   return TKV_OK;
 }
 

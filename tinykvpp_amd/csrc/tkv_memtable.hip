@@ -14,7 +14,7 @@
 //   of the steps before it from a per-wave LDS row only that wave touches, the waves before it from a
 //   sum over the rows: no atomics, so the order within a bucket is the entry order and the pass is
 //   stable. Mode 0 writes the workgroup's bucket sizes to the digit-major matrix hist[digit][workgroup],
-//   whose u64 exclusive scan (scan_level / scan_add, tkv_wal_copy.h) is every bucket's base, mode 1
+//   whose u64 exclusive scan (scan_level / scan_add, tkv_scan.h) is every bucket's base, mode 1
 //   scatters to it; mode 2 does both for a list that fits one workgroup. The scatter first puts the
 //   workgroup's entries into bucket order in LDS and stores from there, so that neighbouring lanes store
 //   to neighbouring addresses of a bucket.
@@ -42,6 +42,7 @@
 #include "tkv_device_util.h"
 #include "tkv_engine.h"
 #include "tkv_memtable_layout.h"
+#include "tkv_scan.h"
 #include "tkv_wal_copy.h"
 #include "tkv_wal_emit.h"
 
@@ -443,26 +444,12 @@ struct MtSrc {
 
 // ---- host side --------------------------------------------------------------------------------------
 
-struct Buf {
-  void* p = nullptr;
-  std::uint64_t cap = 0;
-  ~Buf() { (void)hipFree(p); }
-};
-
 // Per-device scratch, grown by doubling and kept between calls (guarded by mu).
-struct MtScratch {
-  std::mutex mu;
-  Buf kw[2], kx[2], rec[2], apos[2];  // the lists (ping-pong) and the positions of their entries
-  Buf perm, eqn, scan, sums_a, sums_b, hist, hsums;
-  Buf pre, meta, tile;
-  unsigned long long* st = nullptr;
-  std::uint64_t* h_res = nullptr;   // pinned, kMtHres words
-  std::uint64_t* d_hres = nullptr;  // device view of h_res
-  int ncu = 0;
-  ~MtScratch() {
-    (void)hipFree(st);
-    (void)hipHostFree(h_res);
-  }
+struct MtScratch : ScratchBase {
+  DeviceBuf kw[2], kx[2], rec[2], apos[2];  // the lists (ping-pong) and the positions of their entries
+  DeviceBuf perm, eqn, scan, sums_a, sums_b, hist, hsums;
+  DeviceBuf pre, meta, tile;
+  unsigned long long*& st = words;
 };
 
 // What the calling thread's last device build did (tkv_debug_memtable_last).
@@ -472,63 +459,19 @@ thread_local std::uint64_t g_mt_last[4] = {0, 0, 0, 0};
 thread_local int g_mt_timing = 0;
 thread_local double g_mt_phase[4] = {0, 0, 0, 0};
 
-struct PhaseClock {
-  hipEvent_t e[5] = {};
-  bool on = false;
-  hipStream_t st;
-  explicit PhaseClock(hipStream_t s) : st(s) {
-    if (!g_mt_timing) return;
-    on = true;
-    for (auto& x : e) on = on && hipEventCreate(&x) == hipSuccess;
-  }
-  void mark(int k) {
-    if (on) (void)hipEventRecord(e[k], st);
-  }
-  void finish() {  // after the stream has been synchronised
-    for (int k = 0; k < 4; ++k) {
-      float ms = 0;
-      g_mt_phase[k] = on && hipEventElapsedTime(&ms, e[k], e[k + 1]) == hipSuccess ? ms : 0.0;
-    }
-  }
-  ~PhaseClock() {
-    for (auto& x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
-
-int scratch(MtScratch** out) {
-  MtScratch* sp = nullptr;
-  if (int rc = per_device(&sp)) return rc;
-  std::lock_guard<std::mutex> lk(sp->mu);
-  if (!sp->st) {
-    sp->ncu = device_cu_count();
-    if (sp->ncu <= 0) return set_error(TKV_IO_ERROR, "no device");
-    TKV_HIP_RC(hipHostMalloc(reinterpret_cast<void**>(&sp->h_res), kMtHres * sizeof(std::uint64_t), hipHostMallocDefault));
-    TKV_HIP_RC(hipHostGetDevicePointer(reinterpret_cast<void**>(&sp->d_hres), sp->h_res, 0));
-    TKV_HIP_RC(hipMalloc(reinterpret_cast<void**>(&sp->st), kStWords * sizeof(unsigned long long)));
-  }
-  *out = sp;
-  return TKV_OK;
-}
-
 // A failed allocation is the caller's TKV_OUT_OF_MEMORY.
 thread_local std::uint64_t g_taken = 0;  // scratch bytes the calling thread's build in progress asked for
 template <class T>
-int take(Buf& b, std::uint64_t want, T** out) {
-  if (grow(&b.p, &b.cap, want, sizeof(T)) != TKV_OK)
-    return set_error(TKV_OUT_OF_MEMORY, "memtable build: scratch allocation failed");
+int take(DeviceBuf& b, std::uint64_t want, T** out) {
+  if (b.take(want, out) != TKV_OK) return set_error(TKV_OUT_OF_MEMORY, "memtable build: scratch allocation failed");
   g_taken += want * sizeof(T);
-  *out = static_cast<T*>(b.p);
   return TKV_OK;
 }
 
 // In-place exclusive scan whose level 0 has been launched: the levels above it, then the bases back down.
 void scan_rest(const ScanPlan& plan, std::uint64_t* const* lv, hipStream_t st) {
-  for (int k = 1; k < plan.levels; ++k)
-    hipLaunchKernelGGL(scan_level, dim3(static_cast<unsigned>(plan.m[k + 1])), dim3(kScanThreads), 0, st, lv[k], plan.m[k],
-                       lv[k + 1]);
-  for (int k = plan.levels - 2; k >= 0; --k)
-    hipLaunchKernelGGL(scan_add, dim3(blocks(plan.m[k], kScanThreads)), dim3(kScanThreads), 0, st, lv[k], plan.m[k], lv[k + 1]);
+  scan_up(plan, lv, st);
+  scan_down(plan, lv, st);
 }
 
 // The stable sort of the m entries of l[cur] by the passes whose bits differ somewhere; returns the list
@@ -580,22 +523,16 @@ int build_locked(MtScratch& s, MtArgs a, const MemtableCall& c, hipStream_t st) 
   a.st = s.st;
   const dim3 tb(kScanThreads);
   std::uint64_t tag = 0;
-  auto wait = [&](const char* what) -> int {
-    TKV_HIP_RC(hipGetLastError());
-    TKV_HIP_RC(hipStreamSynchronize(st));
-    if (s.h_res[7] != tag) return set_error(TKV_IO_ERROR, what);
-    return TKV_OK;
-  };
 
   // check and first word
-  PhaseClock clock(st);
+  PhaseClock clock(st, g_mt_timing != 0, g_mt_phase);
   clock.mark(0);
   s.h_res[7] = 0;
   hipLaunchKernelGGL(mt_init, dim3(1), dim3(64), 0, st, s.st);
   TKV_HIP_RC(hipMemsetAsync(a.eqn, 0, n * sizeof(std::uint32_t), st));
   hipLaunchKernelGGL(mt_check, dim3(blocks(n, kScanThreads)), tb, 0, st, a, l[0]);
   hipLaunchKernelGGL(mt_publish, dim3(1), dim3(64), 0, st, s.st, static_cast<const std::uint64_t*>(nullptr), s.d_hres, ++tag);
-  if (int rc = wait("memtable build: the check left no result")) return rc;
+  if (int rc = s.wait(st, 7, tag, "memtable build: the check left no result")) return rc;
   if (s.h_res[1] & kFlagBounds) return set_error(TKV_INVALID_ARGUMENT, "memtable build: a key reaches past keys_size");
   if (s.h_res[1] & kFlagLen) return set_error(TKV_INVALID_ARGUMENT, "memtable build: an internal key would be 2^28 bytes or more");
   *c.n_entries = 0;
@@ -624,7 +561,7 @@ int build_locked(MtScratch& s, MtArgs a, const MemtableCall& c, hipStream_t st) 
     hipLaunchKernelGGL(mt_publish, dim3(1), dim3(64), 0, st, s.st, static_cast<const std::uint64_t*>(lv[rp.levels]), s.d_hres,
                        ++tag);
     if (rounds == 1) clock.mark(1);
-    if (int rc = wait("memtable build: a round left no result")) return rc;
+    if (int rc = s.wait(st, 7, tag, "memtable build: a round left no result")) return rc;
     const std::uint64_t next = s.h_res[4] & 0xFFFFFFFFull;
     if (next > m) return set_error(TKV_IO_ERROR, "memtable build: a round grew its list");
     m = next;
@@ -648,7 +585,7 @@ int build_locked(MtScratch& s, MtArgs a, const MemtableCall& c, hipStream_t st) 
   hipLaunchKernelGGL(mt_publish_sizes, dim3(1), dim3(64), 0, st, static_cast<const std::uint64_t*>(lvC[plan.levels]),
                      static_cast<const std::uint64_t*>(lvL[plan.levels]), s.d_hres, ++tag);
   clock.mark(3);
-  if (int rc = wait("memtable build: the dedupe left no result")) return rc;
+  if (int rc = s.wait(st, 7, tag, "memtable build: the dedupe left no result")) return rc;
   a.m = s.h_res[0];
   a.total = s.h_res[1];
   if (a.m == 0 || a.m > n) return set_error(TKV_IO_ERROR, "memtable build: the dedupe is inconsistent");
@@ -698,7 +635,7 @@ int memtable_build_device_impl(const MemtableCall& c, hipStream_t st) {
   for (auto& v : g_mt_last) v = 0;
   for (auto& v : g_mt_phase) v = 0;
   MtScratch* sp = nullptr;
-  if (int rc = scratch(&sp)) return rc;
+  if (int rc = per_device_scratch(&sp, kMtHres, kStWords, true)) return rc;
   MtArgs a{};
   a.keys = c.keys;
   a.keys_size = c.keys_size;

@@ -4,15 +4,13 @@
 // that writes the whole file image: data blocks cut by the greedy size rule, the index, the footer,
 // every checksum stamped.
 //
-// sst_sizes / scan_level / scan_add (tkv_wal_copy.h): the counted sizes e_i = 8 + kl + vl and the
+// sst_sizes / scan_level / scan_add (tkv_scan.h): the counted sizes e_i = 8 + kl + vl and the
 //   written sizes w_i = vlen(kl) + kl + vlen(vl) + vl, their u64 exclusive prefix scans S and W, and
 //   the flag for a length whose varint would not fit the 4 bytes counted for it.
 // sst_next: J[s] = the entry that starts the block after one that starts at s (binary search in S;
 //   the sink is n).
-// sst_double: the chain 0, J(0), J(J(0)), ... marked by pointer doubling: in round k every marked s
-//   marks J_k[s] and J_{k+1} = J_k o J_k goes to the other ping-pong buffer. After round k every chain
-//   member at distance < 2^(k+1) is marked; a mark written and read within one round only adds true
-//   members. The host runs ceil(log2(Bmax + 1)) rounds, Bmax = min(n, S[n] / T + 1).
+// chain_double (tkv_scan.h): the chain 0, J(0), J(J(0)), ... marked by pointer doubling over [0, n] in
+//   ceil(log2(Bmax + 1)) rounds, Bmax = min(n, S[n] / T + 1).
 // sst_marks + scan: the block of every entry and the first entry of every block; sst_blocks: every
 //   block's offset, size, body base; sst_index_sizes + scan: the index entries' offsets.
 // sst_publish: {file_size, B, index_offset, index_size, flags} to a pinned block; the host decides
@@ -35,6 +33,7 @@
 #include "tkv_crc32_device.h"
 #include "tkv_device_util.h"
 #include "tkv_engine.h"
+#include "tkv_scan.h"
 #include "tkv_sst_layout.h"
 #include "tkv_wal_copy.h"
 
@@ -146,17 +145,6 @@ __global__ __launch_bounds__(kScanThreads) void sst_next(SstArgs a) {
     else lo = mid + 1u;
   }
   a.J[s] = static_cast<std::uint32_t>(lo);
-}
-
-// One doubling round over [0, n]: marked entries mark their jump target, the jump composed with itself
-// goes to the other buffer (in place it would skip members).
-__global__ __launch_bounds__(kScanThreads) void sst_double(const std::uint32_t* in, std::uint32_t* out, std::uint32_t* mark,
-                                                           std::uint64_t n) {
-  const std::uint64_t s = blockIdx.x * static_cast<std::uint64_t>(kScanThreads) + threadIdx.x;
-  if (s > n) return;
-  const std::uint32_t j = in[s];  // <= n
-  if (mark[s]) mark[j] = 1u;
-  out[s] = in[j];
 }
 
 // Level 0 of the mark scan over [0, n): the blocks in front of every entry.
@@ -401,27 +389,13 @@ __global__ __launch_bounds__(kScanThreads) void sst_stamp(SstArgs a) {
 
 // ---- host side --------------------------------------------------------------------------------------
 
-struct Buf {
-  void* p = nullptr;
-  std::uint64_t cap = 0;
-  ~Buf() { (void)hipFree(p); }
-};
-
 // Per-device scratch, grown by doubling and kept between calls (guarded by mu).
-struct SstScratch {
-  std::mutex mu;
-  Buf S, W, J, Ja, Jb, mark, blk;              // per entry
-  Buf sums_a, sums_b;                          // scan levels above the first
-  Buf bfirst, boff, bsize, bbase, ioff, bcrc;  // per block
-  Buf tile;
-  unsigned long long* flags = nullptr;
-  std::uint64_t* h_res = nullptr;   // pinned, kSstHres words
-  std::uint64_t* d_hres = nullptr;  // device view of h_res
-  int ncu = 0;
-  ~SstScratch() {
-    (void)hipFree(flags);
-    (void)hipHostFree(h_res);
-  }
+struct SstScratch : ScratchBase {
+  DeviceBuf S, W, J, Ja, Jb, mark, blk;              // per entry
+  DeviceBuf sums_a, sums_b;                          // scan levels above the first
+  DeviceBuf bfirst, boff, bsize, bbase, ioff, bcrc;  // per block
+  DeviceBuf tile;
+  unsigned long long*& flags = words;
 };
 
 // What the calling thread's last device build did (tkv_debug_sst_build_last).
@@ -431,72 +405,15 @@ thread_local std::uint64_t g_sst_last[4] = {0, 0, 0, 0};
 thread_local int g_sst_timing = 0;
 thread_local double g_sst_phase[4] = {0, 0, 0, 0};
 
-struct PhaseClock {
-  hipEvent_t e[5] = {};
-  bool on = false;
-  hipStream_t st;
-  explicit PhaseClock(hipStream_t s) : st(s) {
-    if (!g_sst_timing) return;
-    on = true;
-    for (auto& x : e) on = on && hipEventCreate(&x) == hipSuccess;
-  }
-  void mark(int k) {
-    if (on) (void)hipEventRecord(e[k], st);
-  }
-  void finish() {  // after the stream has been synchronised
-    for (int k = 0; k < 4; ++k) {
-      float ms = 0;
-      g_sst_phase[k] = on && hipEventElapsedTime(&ms, e[k], e[k + 1]) == hipSuccess ? ms : 0.0;
-    }
-  }
-  ~PhaseClock() {
-    for (auto& x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
-
-int scratch(SstScratch** out) {
-  SstScratch* sp = nullptr;
-  if (int rc = per_device(&sp)) return rc;
-  std::lock_guard<std::mutex> lk(sp->mu);
-  if (!sp->flags) {
-    sp->ncu = device_cu_count();
-    TKV_HIP_RC(hipHostMalloc(reinterpret_cast<void**>(&sp->h_res), kSstHres * sizeof(std::uint64_t), hipHostMallocDefault));
-    TKV_HIP_RC(hipHostGetDevicePointer(reinterpret_cast<void**>(&sp->d_hres), sp->h_res, 0));
-    TKV_HIP_RC(hipMalloc(reinterpret_cast<void**>(&sp->flags), sizeof(unsigned long long)));
-  }
-  *out = sp;
-  return TKV_OK;
-}
-
-template <class T>
-int take(Buf& b, std::uint64_t want, T** out) {
-  if (int rc = grow(&b.p, &b.cap, want, sizeof(T))) return rc;
-  *out = static_cast<T*>(b.p);
-  return TKV_OK;
-}
-
-// The levels above the first of a scan whose level 0 has been launched, up to the single total.
-void scan_up(const ScanPlan& plan, std::uint64_t* const* lv, hipStream_t st) {
-  for (int k = 1; k < plan.levels; ++k)
-    hipLaunchKernelGGL(scan_level, dim3(static_cast<unsigned>(plan.m[k + 1])), dim3(kScanThreads), 0, st, lv[k], plan.m[k],
-                       lv[k + 1]);
-}
-// The block bases back down to the entries.
-void scan_down(const ScanPlan& plan, std::uint64_t* const* lv, hipStream_t st) {
-  for (int k = plan.levels - 2; k >= 0; --k)
-    hipLaunchKernelGGL(scan_add, dim3(blocks(plan.m[k], kScanThreads)), dim3(kScanThreads), 0, st, lv[k], plan.m[k], lv[k + 1]);
-}
-
 int build_locked(SstScratch& s, SstArgs a, std::uint64_t cap, std::uint64_t block_cap, std::uint64_t* file_size,
                  std::uint64_t* n_blocks, std::uint64_t* index_offset, std::uint64_t* index_size, hipStream_t st) {
   const std::uint64_t n = a.n, n1 = a.n + 1u;
   const ScanPlan plan(n);
-  if (int rc = take(s.S, n1, &a.S)) return rc;
-  if (int rc = take(s.W, n1, &a.W)) return rc;
+  if (int rc = s.S.take(n1, &a.S)) return rc;
+  if (int rc = s.W.take(n1, &a.W)) return rc;
   std::uint64_t *sums_a = nullptr, *sums_b = nullptr;
-  if (int rc = take(s.sums_a, plan.nsum, &sums_a)) return rc;
-  if (int rc = take(s.sums_b, plan.nsum, &sums_b)) return rc;
+  if (int rc = s.sums_a.take(plan.nsum, &sums_a)) return rc;
+  if (int rc = s.sums_b.take(plan.nsum, &sums_b)) return rc;
   a.flags = s.flags;
   std::uint64_t *lvS[kScanLevels + 1], *lvW[kScanLevels + 1];
   plan.place(a.S, sums_a, lvS);
@@ -505,7 +422,7 @@ int build_locked(SstScratch& s, SstArgs a, std::uint64_t cap, std::uint64_t bloc
   const dim3 gn1(blocks(n1, kScanThreads));
 
   // sizes
-  PhaseClock clock(st);
+  PhaseClock clock(st, g_sst_timing != 0, g_sst_phase);
   clock.mark(0);
   TKV_HIP_RC(hipMemsetAsync(s.flags, 0, sizeof(unsigned long long), st));
   s.h_res[7] = 0;
@@ -515,39 +432,29 @@ int build_locked(SstScratch& s, SstArgs a, std::uint64_t cap, std::uint64_t bloc
   scan_up(plan, lvW, st);
   hipLaunchKernelGGL(sst_publish_sizes, dim3(1), dim3(64), 0, st, a, lvS[plan.levels], s.d_hres);
   clock.mark(1);
-  TKV_HIP_RC(hipGetLastError());
-  TKV_HIP_RC(hipStreamSynchronize(st));
-  if (s.h_res[7] != 1) return set_error(TKV_IO_ERROR, "SSTable build: the size scan left no result");
+  if (int rc = s.wait(st, 7, 1, "SSTable build: the size scan left no result")) return rc;
   if (s.h_res[1] & kFlagLen) return set_error(TKV_INVALID_ARGUMENT, "SSTable build: a key or value length is 2^28 or more");
   const std::uint64_t total = s.h_res[0];
   const std::uint64_t bmax = std::min<std::uint64_t>(n, total / a.T + 1u);
   const std::uint32_t rounds = sst_rounds(bmax);
 
   // cut
-  if (int rc = take(s.J, n1, &a.J)) return rc;
-  if (int rc = take(s.Ja, n1, &a.Ja)) return rc;
-  if (int rc = take(s.Jb, n1, &a.Jb)) return rc;
-  if (int rc = take(s.mark, n1, &a.mark)) return rc;
-  if (int rc = take(s.blk, n1, &a.blk)) return rc;
-  if (int rc = take(s.bfirst, bmax + 1u, &a.bfirst)) return rc;
-  if (int rc = take(s.boff, bmax + 1u, &a.boff)) return rc;
-  if (int rc = take(s.bsize, bmax + 1u, &a.bsize)) return rc;
-  if (int rc = take(s.bbase, bmax + 1u, &a.bbase)) return rc;
-  if (int rc = take(s.ioff, bmax + 1u, &a.ioff)) return rc;
-  if (int rc = take(s.bcrc, bmax + 1u, &a.bcrc)) return rc;
+  if (int rc = s.J.take(n1, &a.J)) return rc;
+  if (int rc = s.Ja.take(n1, &a.Ja)) return rc;
+  if (int rc = s.Jb.take(n1, &a.Jb)) return rc;
+  if (int rc = s.mark.take(n1, &a.mark)) return rc;
+  if (int rc = s.blk.take(n1, &a.blk)) return rc;
+  if (int rc = s.bfirst.take(bmax + 1u, &a.bfirst)) return rc;
+  if (int rc = s.boff.take(bmax + 1u, &a.boff)) return rc;
+  if (int rc = s.bsize.take(bmax + 1u, &a.bsize)) return rc;
+  if (int rc = s.bbase.take(bmax + 1u, &a.bbase)) return rc;
+  if (int rc = s.ioff.take(bmax + 1u, &a.ioff)) return rc;
+  if (int rc = s.bcrc.take(bmax + 1u, &a.bcrc)) return rc;
   a.bmax = bmax;
   scan_down(plan, lvS, st);
   scan_down(plan, lvW, st);
   hipLaunchKernelGGL(sst_next, gn1, tb, 0, st, a);
-  {
-    const std::uint32_t* in = a.J;
-    std::uint32_t* out = a.Ja;
-    for (std::uint32_t r = 0; r < rounds; ++r) {
-      hipLaunchKernelGGL(sst_double, gn1, tb, 0, st, in, out, a.mark, n);
-      in = out;
-      out = out == a.Ja ? a.Jb : a.Ja;
-    }
-  }
+  chain_double(a.J, a.Ja, a.Jb, a.mark, n1, rounds, st);
   std::uint64_t* lvM[kScanLevels + 1];
   plan.place(a.blk, sums_a, lvM);  // (the S levels are done with)
   hipLaunchKernelGGL(sst_marks, g0, tb, 0, st, a, lvM[1]);
@@ -563,9 +470,7 @@ int build_locked(SstScratch& s, SstArgs a, std::uint64_t cap, std::uint64_t bloc
   scan_down(bplan, lvI, st);
   hipLaunchKernelGGL(sst_publish, dim3(1), dim3(64), 0, st, a, lvI[bplan.levels], s.d_hres);
   clock.mark(2);
-  TKV_HIP_RC(hipGetLastError());
-  TKV_HIP_RC(hipStreamSynchronize(st));
-  if (s.h_res[7] != 2) return set_error(TKV_IO_ERROR, "SSTable build: the cut left no result");
+  if (int rc = s.wait(st, 7, 2, "SSTable build: the cut left no result")) return rc;
   const std::uint64_t fsize = s.h_res[0], B = s.h_res[1], ioff = s.h_res[2], isz = s.h_res[3];
   if (B == 0 || B > bmax) return set_error(TKV_IO_ERROR, "SSTable build: the cut is inconsistent");
   if (s.h_res[4] & kFlagBlock) return set_error(TKV_INVALID_ARGUMENT, "SSTable build: a data block does not fit u32");
@@ -584,7 +489,7 @@ int build_locked(SstScratch& s, SstArgs a, std::uint64_t cap, std::uint64_t bloc
   a.index_offset = ioff;
   a.index_size = isz;
   a.ntiles = (ioff + kSstTile - 1u) / kSstTile;
-  if (int rc = take(s.tile, 4u * a.ntiles, &a.tile)) return rc;
+  if (int rc = s.tile.take(4u * a.ntiles, &a.tile)) return rc;
   hipLaunchKernelGGL(sst_positions, dim3(blocks(n, kScanThreads)), tb, 0, st, a);
   hipLaunchKernelGGL(sst_tiles, dim3(blocks(a.ntiles, kScanThreads)), tb, 0, st, a);
   const std::uint64_t want = (a.ntiles + kSstWaves - 1u) / kSstWaves;
@@ -621,7 +526,7 @@ int sst_build_device_impl(const std::uint8_t* d_keys, const std::uint64_t* d_key
   for (auto& v : g_sst_phase) v = 0;
   if (!device_tables(kAlgoCrc32)) return TKV_IO_ERROR;
   SstScratch* sp = nullptr;
-  if (int rc = scratch(&sp)) return rc;
+  if (int rc = per_device_scratch(&sp, kSstHres, 1, false)) return rc;
   SstArgs a{};
   a.keys = d_keys;
   a.key_off = d_key_off;

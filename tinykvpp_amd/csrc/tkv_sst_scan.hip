@@ -7,8 +7,8 @@
 //   publishes them; the host needs B and index_size for the launches below. The index is a chain of
 //   length-prefixed strings: scn_next computes J[p] = where the entry that starts at index byte p ends,
 //   for every byte p (an entry that fails its checks jumps to the sink index_size + 1, index_size jumps
-//   to itself), sst_double (the flush's doubling round) marks the chain from byte 8 in
-//   ceil(log2(B + 2)) rounds, a u64 scan of the marks ranks the entries, and scn_blocks reads off / size
+//   to itself), chain_double (tkv_scan.h, shared with the flush) marks the chain from byte 8 in
+//   ceil(log2(B + 2)) rounds, a u64 scan of the marks (tkv_scan.h) ranks the entries, and scn_blocks reads off / size
 //   of every marked entry, one thread each. The framing holds when exactly B entries are marked, the
 //   sink is not, and every block lies in the data region (scn_index_verdict).
 // Checksum. One batch_device_impl call folds the B block images and, as entry B, the footer's span
@@ -36,6 +36,7 @@
 #include "tkv_crc32_device.h"
 #include "tkv_device_util.h"
 #include "tkv_engine.h"
+#include "tkv_scan.h"
 #include "tkv_sst_layout.h"
 #include "tkv_wal_copy.h"
 #include "tkv_wal_emit.h"
@@ -161,17 +162,6 @@ __global__ __launch_bounds__(kScanThreads) void scn_next(ScanArgs a) {
     if (s.ok) j = static_cast<std::uint32_t>(s.next);
   }
   a.J[p] = j;
-}
-
-// One doubling round over [0, m): marked positions mark their jump target, the jump composed with itself
-// goes to the other buffer (the flush's sst_double).
-__global__ __launch_bounds__(kScanThreads) void scn_double(const std::uint32_t* in, std::uint32_t* out, std::uint32_t* mark,
-                                                           std::uint64_t m) {
-  const std::uint64_t s = blockIdx.x * static_cast<std::uint64_t>(kScanThreads) + threadIdx.x;
-  if (s >= m) return;
-  const std::uint32_t j = in[s];  // < m
-  if (mark[s]) mark[j] = 1u;
-  out[s] = in[j];
 }
 
 // Level 0 of the mark scan over [0, isz): the entries in front of every index byte.
@@ -423,89 +413,25 @@ struct SstSrc {
 
 // ---- host side --------------------------------------------------------------------------------------
 
-struct Buf {
-  void* p = nullptr;
-  std::uint64_t cap = 0;
-  ~Buf() { (void)hipFree(p); }
-};
-
 // Per-device scratch, grown by doubling and kept between calls (guarded by mu): 24 bytes per index byte,
 // 52 per block, 40 per entry, 8 per 4 KiB of a copied arena.
-struct ScnScratch {
-  std::mutex mu;
-  Buf J, Ja, Jb, mark, rank;                      // per index byte
-  Buf boff, bsize, bcrc, ikey, ikl, bfirst, bks, bvs, bsums;  // per block
-  Buf kpos, vpos, klen, vlen, kpre, vpre;         // per entry
-  Buf sums_a, sums_b, ktile, vtile;
-  unsigned long long* w = nullptr;
-  std::uint64_t* h_res = nullptr;   // pinned, kScnHres words
-  std::uint64_t* d_hres = nullptr;  // device view of h_res
-  int ncu = 0;
-  ~ScnScratch() {
-    (void)hipFree(w);
-    (void)hipHostFree(h_res);
-  }
+struct ScnScratch : ScratchBase {
+  DeviceBuf J, Ja, Jb, mark, rank;                      // per index byte
+  DeviceBuf boff, bsize, bcrc, ikey, ikl, bfirst, bks, bvs, bsums;  // per block
+  DeviceBuf kpos, vpos, klen, vlen, kpre, vpre;         // per entry
+  DeviceBuf sums_a, sums_b, ktile, vtile;
+  unsigned long long*& w = words;
 };
 
 thread_local int g_scn_timing = 0;
 thread_local double g_scn_phase[4] = {0, 0, 0, 0};
 thread_local std::uint64_t g_scn_last[4] = {0, 0, 0, 0};
 
-struct ScnClock {
-  hipEvent_t e[5] = {};
-  bool on = false;
-  hipStream_t st;
-  explicit ScnClock(hipStream_t s) : st(s) {
-    if (!g_scn_timing) return;
-    on = true;
-    for (auto& x : e) on = on && hipEventCreate(&x) == hipSuccess;
-  }
-  void mark(int k) {
-    if (on) (void)hipEventRecord(e[k], st);
-  }
-  void finish() {  // after the stream has been synchronised
-    for (int k = 0; k < 4; ++k) {
-      float ms = 0;
-      g_scn_phase[k] = on && hipEventElapsedTime(&ms, e[k], e[k + 1]) == hipSuccess ? ms : 0.0;
-    }
-  }
-  ~ScnClock() {
-    for (auto& x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
-
-int scratch(ScnScratch** out) {
-  ScnScratch* sp = nullptr;
-  if (int rc = per_device(&sp)) return rc;
-  std::lock_guard<std::mutex> lk(sp->mu);
-  if (!sp->w) {
-    sp->ncu = device_cu_count();
-    if (sp->ncu <= 0) return set_error(TKV_IO_ERROR, "no device");
-    TKV_HIP_RC(hipHostMalloc(reinterpret_cast<void**>(&sp->h_res), kScnHres * sizeof(std::uint64_t), hipHostMallocDefault));
-    TKV_HIP_RC(hipHostGetDevicePointer(reinterpret_cast<void**>(&sp->d_hres), sp->h_res, 0));
-    TKV_HIP_RC(hipMalloc(reinterpret_cast<void**>(&sp->w), 8 * sizeof(unsigned long long)));
-  }
-  *out = sp;
-  return TKV_OK;
-}
-
 // A failed allocation is the caller's TKV_OUT_OF_MEMORY.
 template <class T>
-int take(Buf& b, std::uint64_t want, T** out) {
-  if (grow(&b.p, &b.cap, want, sizeof(T)) != TKV_OK) return set_error(TKV_OUT_OF_MEMORY, "SSTable scan: scratch allocation failed");
-  *out = static_cast<T*>(b.p);
+int take(DeviceBuf& b, std::uint64_t want, T** out) {
+  if (b.take(want, out) != TKV_OK) return set_error(TKV_OUT_OF_MEMORY, "SSTable scan: scratch allocation failed");
   return TKV_OK;
-}
-
-void scan_up(const ScanPlan& plan, std::uint64_t* const* lv, hipStream_t st) {
-  for (int k = 1; k < plan.levels; ++k)
-    hipLaunchKernelGGL(scan_level, dim3(static_cast<unsigned>(plan.m[k + 1])), dim3(kScanThreads), 0, st, lv[k], plan.m[k],
-                       lv[k + 1]);
-}
-void scan_down(const ScanPlan& plan, std::uint64_t* const* lv, hipStream_t st) {
-  for (int k = plan.levels - 2; k >= 0; --k)
-    hipLaunchKernelGGL(scan_add, dim3(blocks(plan.m[k], kScanThreads)), dim3(kScanThreads), 0, st, lv[k], plan.m[k], lv[k + 1]);
 }
 
 struct ScanOut {
@@ -526,15 +452,13 @@ int corrupted(const ScanOut& o, std::uint64_t bad, const char* msg) {
 int scan_locked(ScnScratch& s, ScanArgs a, const ScanOut& o, hipStream_t st) {
   const dim3 tb(kScanThreads);
   a.w = s.w;
-  ScnClock clock(st);
+  PhaseClock clock(st, g_scn_timing != 0, g_scn_phase);
   clock.mark(0);
 
   // open
   s.h_res[7] = 0;
   hipLaunchKernelGGL(scn_open, dim3(1), dim3(64), 0, st, a, s.d_hres);
-  TKV_HIP_RC(hipGetLastError());
-  TKV_HIP_RC(hipStreamSynchronize(st));
-  if (s.h_res[7] != 1) return set_error(TKV_IO_ERROR, "SSTable scan: the open left no result");
+  if (int rc = s.wait(st, 7, 1, "SSTable scan: the open left no result")) return rc;
   if (!s.h_res[3]) return corrupted(o, TKV_SST_BAD_FOOTER, "SSTable scan: the footer does not describe this file");
   a.ioff = s.h_res[0];
   a.isz = s.h_res[1];
@@ -563,24 +487,14 @@ int scan_locked(ScnScratch& s, ScanArgs a, const ScanOut& o, hipStream_t st) {
   a.nmark = lvM[iplan.levels];
   const std::uint32_t rounds = sst_rounds(B + 1u);
   hipLaunchKernelGGL(scn_next, dim3(blocks(nidx, kScanThreads)), tb, 0, st, a);
-  {
-    const std::uint32_t* in = a.J;
-    std::uint32_t* out = a.Ja;
-    for (std::uint32_t r = 0; r < rounds; ++r) {
-      hipLaunchKernelGGL(scn_double, dim3(blocks(nidx, kScanThreads)), tb, 0, st, in, out, a.mark, nidx);
-      in = out;
-      out = out == a.Ja ? a.Jb : a.Ja;
-    }
-  }
+  chain_double(a.J, a.Ja, a.Jb, a.mark, nidx, rounds, st);
   hipLaunchKernelGGL(scn_marks, dim3(static_cast<unsigned>(iplan.m[1])), tb, 0, st, a, lvM[1]);
   scan_up(iplan, lvM, st);
   scan_down(iplan, lvM, st);
   if (index_ok) hipLaunchKernelGGL(scn_blocks, dim3(blocks(a.isz, kScanThreads)), tb, 0, st, a);
   hipLaunchKernelGGL(scn_index_verdict, dim3(1), dim3(64), 0, st, a, s.d_hres);
   clock.mark(1);
-  TKV_HIP_RC(hipGetLastError());
-  TKV_HIP_RC(hipStreamSynchronize(st));
-  if (s.h_res[7] != 2) return set_error(TKV_IO_ERROR, "SSTable scan: the index pass left no result");
+  if (int rc = s.wait(st, 7, 2, "SSTable scan: the index pass left no result")) return rc;
   index_ok = index_ok && s.h_res[0] != 0;
 
   // checksum: the block images and the footer's span in one batch
@@ -618,9 +532,7 @@ int scan_locked(ScnScratch& s, ScanArgs a, const ScanOut& o, hipStream_t st) {
     const std::uint64_t* none = nullptr;
     hipLaunchKernelGGL(scn_publish, dim3(1), dim3(64), 0, st, a, none, none, none, s.d_hres);
   }
-  TKV_HIP_RC(hipGetLastError());
-  TKV_HIP_RC(hipStreamSynchronize(st));
-  if (s.h_res[7] != 3) return set_error(TKV_IO_ERROR, "SSTable scan: the parse left no result");
+  if (int rc = s.wait(st, 7, 3, "SSTable scan: the parse left no result")) return rc;
   if (s.h_res[0] & kBadFooterCrc) return corrupted(o, TKV_SST_BAD_FOOTER, "SSTable scan: corrupted index or footer");
   if (!index_ok) return corrupted(o, TKV_SST_BAD_INDEX, "SSTable scan: the index framing does not hold");
   if (s.h_res[1] < B) return corrupted(o, s.h_res[1], "SSTable scan: corrupted data block");
@@ -715,7 +627,7 @@ int sst_scan_device_impl(const std::uint8_t* d_file, std::uint64_t file_size, st
   for (auto& v : g_scn_phase) v = 0;
   if (!device_tables(kAlgoCrc32)) return TKV_IO_ERROR;
   ScnScratch* sp = nullptr;
-  if (int rc = scratch(&sp)) return rc;
+  if (int rc = per_device_scratch(&sp, kScnHres, 8, true)) return rc;
   ScanArgs a{};
   a.file = d_file;
   a.size = file_size;

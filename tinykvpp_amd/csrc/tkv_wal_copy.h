@@ -1,9 +1,8 @@
-// Device pieces shared by the WAL group-commit encoder (tkv_wal_encode.hip) and the batched WAL decode
-// (tkv_wal_decode.hip): the levels of a u64 exclusive scan over n entries (kScanBlock entries per
-// workgroup, the block sums scanned by the next level) with their host-side plan, and the copy of byte
-// spans at any source / destination alignment into a wave's LDS window and of the window's tile out to
-// memory (one span per lane, or one span by the whole wave; loads touch only source granules that hold
-// a byte of the span).
+// Device pieces shared by the WAL group-commit encoder (tkv_wal_encode.hip), the batched WAL decode
+// (tkv_wal_decode.hip) and the SSTable flush (tkv_sst_build.hip): the copy of byte spans at any source /
+// destination alignment into a wave's LDS window and of the window's tile out to memory (one span per
+// lane, or one span by the whole wave; loads touch only source granules that hold a byte of the span).
+// Includes the u64 scan its users run in front of their copies (tkv_scan.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,77 +10,18 @@
 #include <cstdint>
 
 #include "tkv_crc32_device.h"
+#include "tkv_scan.h"
 
 namespace tkv {
 namespace {
 
 constexpr std::uint32_t kShortSpan = 64;      // keys / values up to this long are copied by their record's lane
-constexpr unsigned kScanThreads = 256;
-constexpr unsigned kScanItems = 4;            // consecutive entries per thread
-constexpr std::uint64_t kScanBlock = kScanThreads * kScanItems;  // entries per workgroup of a scan level
-constexpr int kScanLevels = 4;                // kScanBlock^4 >= 2^32 entries
 
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-
-// ---- scan levels ------------------------------------------------------------------------------------
-
-// The thread's kScanItems consecutive entries v (entry i0 + k; zero past m) of one workgroup of a scan
-// level: their exclusive prefix within the block to arr[i0 + k], the block's sum to bsum[block].
-__device__ __forceinline__ void scan_items(const std::uint64_t (&v)[kScanItems], std::uint64_t i0, std::uint64_t m,
-                                           std::uint64_t* arr, std::uint64_t* bsum) {
-  std::uint64_t s = 0;
-#pragma unroll
-  for (unsigned k = 0; k < kScanItems; ++k) s += v[k];
-  std::uint64_t total;
-  std::uint64_t run = dev::block_prefix<std::uint64_t, kScanThreads>(s, &total);
-#pragma unroll
-  for (unsigned k = 0; k < kScanItems; ++k) {
-    const std::uint64_t i = i0 + k;
-    if (i < m) arr[i] = run;
-    run += v[k];
-  }
-  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-// A level above the first: arr[0, m) (the block sums of the level below) in place.
-__global__ __launch_bounds__(kScanThreads) void scan_level(std::uint64_t* arr, std::uint64_t m, std::uint64_t* bsum) {
-  const std::uint64_t i0 = blockIdx.x * kScanBlock + threadIdx.x * kScanItems;
-  std::uint64_t v[kScanItems];
-#pragma unroll
-  for (unsigned k = 0; k < kScanItems; ++k) v[k] = i0 + k < m ? arr[i0 + k] : 0u;
-  scan_items(v, i0, m, arr, bsum);
-}
-
-__global__ __launch_bounds__(kScanThreads) void scan_add(std::uint64_t* arr, std::uint64_t m, const std::uint64_t* base) {
-  const std::uint64_t i = blockIdx.x * static_cast<std::uint64_t>(kScanThreads) + threadIdx.x;
-  if (i < m) arr[i] += base[i / kScanBlock];
-}
-
-// Entries of the scan levels over n: level k + 1 holds the block sums of level k, the last one a single
-// sum. nsum = the entries of the levels above the first.
-struct ScanPlan {
-  std::uint64_t m[kScanLevels + 1];
-  int levels = 0;
-  std::uint64_t nsum = 0;
-  explicit ScanPlan(std::uint64_t n) {
-    m[0] = n;
-    while (m[levels] > 1u || levels == 0) {
-      m[levels + 1] = (m[levels] + kScanBlock - 1u) / kScanBlock;
-      ++levels;
-    }
-    for (int k = 1; k <= levels; ++k) nsum += m[k];
-  }
-  // lv[0] = the entries, lv[k] for k >= 1 laid one after the other in sums (nsum entries).
-  void place(std::uint64_t* entries, std::uint64_t* sums, std::uint64_t* (&lv)[kScanLevels + 1]) const {
-    lv[0] = entries;
-    lv[1] = sums;
-    for (int k = 2; k <= levels; ++k) lv[k] = lv[k - 1] + m[k - 1];
-  }
-};
 
 // ---- spans into an LDS window -----------------------------------------------------------------------
 

@@ -8,7 +8,7 @@
 // that hold the record's 26 header bytes, realigns them in registers (lane_dwords_n: two selects and
 // v_alignbyte) and runs wal_entry::decode's structural checks in 64-bit arithmetic. It runs twice.
 // dec_scan: the header pass as level 0 of two u64 exclusive scans over n, keys and values, in one launch
-// (scan_items; the levels above and their plan are tkv_wal_copy.h's, as for the encoder), and the
+// (scan_items; the levels above and their plan are tkv_scan.h's, as for the encoder), and the
 // atomic minimum of the failing indices. The host reads {keys total, values total, first bad} from a
 // pinned block and decides corrupted / overflow before anything is written for the caller.
 // dec_finish: the header pass again: the fixed-width columns, the final arena offsets, and per copied
@@ -29,6 +29,7 @@
 #include "tkv_crc32_device.h"
 #include "tkv_device_util.h"
 #include "tkv_engine.h"
+#include "tkv_scan.h"
 #include "tkv_wal_copy.h"
 #include "tkv_wal_emit.h"
 #include "tkv_wal_device.h"
@@ -212,46 +213,17 @@ struct WalSrc {
 // ---- host side --------------------------------------------------------------------------------------
 
 // Per-device scratch, grown by doubling and kept between calls (guarded by mu).
-struct DecScratch {
-  std::mutex mu;
-  std::uint64_t cap_kpre = 0, cap_vpre = 0, cap_sum = 0, cap_ktile = 0, cap_vtile = 0;
-  void* kpre = nullptr;   // key arena offsets (u64, n + 1)
-  void* vpre = nullptr;   // value arena offsets
-  void* sums = nullptr;   // block sums of every scan level, keys then values
-  void* ktile = nullptr;  // first and last record of every tile (2 x u32)
-  void* vtile = nullptr;
-  unsigned long long* first_bad = nullptr;
-  std::uint64_t* h_res = nullptr;   // pinned, kDecHres words
-  std::uint64_t* d_hres = nullptr;  // device view of h_res
-  int ncu = 0;
-  ~DecScratch() {
-    (void)hipFree(kpre);
-    (void)hipFree(vpre);
-    (void)hipFree(sums);
-    (void)hipFree(ktile);
-    (void)hipFree(vtile);
-    (void)hipFree(first_bad);
-    (void)hipHostFree(h_res);
-  }
+struct DecScratch : ScratchBase {
+  DeviceBuf kpre;   // key arena offsets (u64, n + 1)
+  DeviceBuf vpre;   // value arena offsets
+  DeviceBuf sums;   // block sums of every scan level, keys then values
+  DeviceBuf ktile;  // first and last record of every tile (2 x u32)
+  DeviceBuf vtile;
+  unsigned long long*& first_bad = words;
 };
 
 // What the calling thread's last device decode did (tkv_debug_wal_decode_last).
 thread_local std::uint64_t g_dec_last[4] = {0, 0, 0, 0};
-
-int scratch(DecScratch** out) {
-  DecScratch* sp = nullptr;
-  if (int rc = per_device(&sp)) return rc;
-  std::lock_guard<std::mutex> lk(sp->mu);
-  if (!sp->first_bad) {
-    sp->ncu = device_cu_count();
-    if (sp->ncu <= 0) return set_error(TKV_IO_ERROR, "no device");
-    TKV_HIP_RC(hipHostMalloc(reinterpret_cast<void**>(&sp->h_res), kDecHres * sizeof(std::uint64_t), hipHostMallocDefault));
-    TKV_HIP_RC(hipHostGetDevicePointer(reinterpret_cast<void**>(&sp->d_hres), sp->h_res, 0));
-    TKV_HIP_RC(hipMalloc(reinterpret_cast<void**>(&sp->first_bad), sizeof(unsigned long long)));
-  }
-  *out = sp;
-  return TKV_OK;
-}
 
 // The emit of one copied arena; returns its waves.
 template <bool VAL>
@@ -275,27 +247,21 @@ int decode_locked(DecScratch& s, DecArgs a, std::uint8_t* d_keys, std::uint64_t 
   }
   const ScanPlan plan(a.n);
   const int levels = plan.levels;
-  const std::uint64_t* m = plan.m;
-  if (int rc = grow(&s.kpre, &s.cap_kpre, a.n + 1u, 8)) return rc;
-  if (int rc = grow(&s.vpre, &s.cap_vpre, a.n + 1u, 8)) return rc;
-  if (int rc = grow(&s.sums, &s.cap_sum, 2u * plan.nsum, 8)) return rc;
-  a.kpre = static_cast<std::uint64_t*>(s.kpre);
-  a.vpre = static_cast<std::uint64_t*>(s.vpre);
+  std::uint64_t* sums = nullptr;
+  if (int rc = s.kpre.take(a.n + 1u, &a.kpre)) return rc;
+  if (int rc = s.vpre.take(a.n + 1u, &a.vpre)) return rc;
+  if (int rc = s.sums.take(2u * plan.nsum, &sums)) return rc;
   a.first_bad = s.first_bad;
   std::uint64_t *klv[kScanLevels + 1], *vlv[kScanLevels + 1];
-  plan.place(a.kpre, static_cast<std::uint64_t*>(s.sums), klv);
-  plan.place(a.vpre, static_cast<std::uint64_t*>(s.sums) + plan.nsum, vlv);
+  plan.place(a.kpre, sums, klv);
+  plan.place(a.vpre, sums + plan.nsum, vlv);
   s.h_res[3] = 0;
   hipLaunchKernelGGL(dec_init, dim3(1), dim3(64), 0, st, s.first_bad, a.n);
-  hipLaunchKernelGGL(dec_scan, dim3(static_cast<unsigned>(m[1])), dim3(kScanThreads), 0, st, a, klv[1], vlv[1]);
-  for (int k = 1; k < levels; ++k) {
-    hipLaunchKernelGGL(scan_level, dim3(static_cast<unsigned>(m[k + 1])), dim3(kScanThreads), 0, st, klv[k], m[k], klv[k + 1]);
-    hipLaunchKernelGGL(scan_level, dim3(static_cast<unsigned>(m[k + 1])), dim3(kScanThreads), 0, st, vlv[k], m[k], vlv[k + 1]);
-  }
+  hipLaunchKernelGGL(dec_scan, dim3(static_cast<unsigned>(plan.m[1])), dim3(kScanThreads), 0, st, a, klv[1], vlv[1]);
+  scan_up(plan, klv, st);
+  scan_up(plan, vlv, st);
   hipLaunchKernelGGL(dec_publish, dim3(1), dim3(64), 0, st, klv[levels], vlv[levels], s.first_bad, s.d_hres);
-  TKV_HIP_RC(hipGetLastError());
-  TKV_HIP_RC(hipStreamSynchronize(st));
-  if (s.h_res[3] != 1) return set_error(TKV_IO_ERROR, "WAL decode: the header pass left no result");
+  if (int rc = s.wait(st, 3, 1, "WAL decode: the header pass left no result")) return rc;
   if (s.h_res[2] < a.n) {
     *first_bad = s.h_res[2];
     return set_error(TKV_CORRUPTED, "WAL decode: a record fails wal_entry::decode's structural checks");
@@ -308,16 +274,14 @@ int decode_locked(DecScratch& s, DecArgs a, std::uint8_t* d_keys, std::uint64_t 
   if ((kcopy && a.ktotal > keys_cap) || (vcopy && a.vtotal > vals_cap))
     return set_error(TKV_BUFFER_OVERFLOW, "WAL decode: an arena does not fit its cap");
   if ((kcopy && !d_keys) || (vcopy && !d_vals)) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  a.ktile = static_cast<std::uint32_t*>(s.ktile.p);  // (an arena left as views keeps an earlier call's table: not read)
+  a.vtile = static_cast<std::uint32_t*>(s.vtile.p);
   if (kcopy)
-    if (int rc = grow(&s.ktile, &s.cap_ktile, (a.ktotal + kDecTile - 1u) / kDecTile, 8)) return rc;
+    if (int rc = s.ktile.take(2u * ((a.ktotal + kDecTile - 1u) / kDecTile), &a.ktile)) return rc;
   if (vcopy)
-    if (int rc = grow(&s.vtile, &s.cap_vtile, (a.vtotal + kDecTile - 1u) / kDecTile, 8)) return rc;
-  a.ktile = static_cast<std::uint32_t*>(s.ktile);
-  a.vtile = static_cast<std::uint32_t*>(s.vtile);
-  for (int k = levels - 2; k >= 1; --k) {
-    hipLaunchKernelGGL(scan_add, dim3(blocks(m[k], kScanThreads)), dim3(kScanThreads), 0, st, klv[k], m[k], klv[k + 1]);
-    hipLaunchKernelGGL(scan_add, dim3(blocks(m[k], kScanThreads)), dim3(kScanThreads), 0, st, vlv[k], m[k], vlv[k + 1]);
-  }
+    if (int rc = s.vtile.take(2u * ((a.vtotal + kDecTile - 1u) / kDecTile), &a.vtile)) return rc;
+  scan_down(plan, klv, st, 1);  // (dec_finish adds klv[1] and vlv[1] itself)
+  scan_down(plan, vlv, st, 1);
   hipLaunchKernelGGL(dec_finish, dim3(blocks(a.n, kScanThreads)), dim3(kScanThreads), 0, st, a,
                      levels > 1 ? klv[1] : static_cast<const std::uint64_t*>(nullptr),
                      levels > 1 ? vlv[1] : static_cast<const std::uint64_t*>(nullptr));
@@ -343,7 +307,7 @@ int wal_decode_device_impl(const std::uint8_t* d_img, std::uint64_t size, const 
                            std::uint64_t* first_bad, hipStream_t st) {
   for (auto& v : g_dec_last) v = 0;
   DecScratch* sp = nullptr;
-  if (int rc = scratch(&sp)) return rc;
+  if (int rc = per_device_scratch(&sp, kDecHres, 1, true)) return rc;
   DecArgs a{};
   a.img = d_img;
   a.size = size;

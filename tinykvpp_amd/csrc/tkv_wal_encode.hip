@@ -5,7 +5,7 @@
 // (little-endian, packed), record_len = 18 + key_len + val_len, crc32 = CRC-32 of bytes [8, 8 + record_len),
 // and the records lie back to back in batch order.
 //
-// enc_scan / scan_level / scan_add (the levels: tkv_wal_copy.h): record sizes and their u64 exclusive prefix scan over n, kScanBlock records per
+// enc_scan / scan_level / scan_add (the levels: tkv_scan.h): record sizes and their u64 exclusive prefix scan over n, kScanBlock records per
 // workgroup (DPP prefix per wave, wave totals through LDS), the block sums scanned by the next level,
 // up to kScanLevels levels. The host reads {total, overflow flag, long records} from a pinned block
 // and decides overflow / invalid before anything is written for the caller.
@@ -35,6 +35,7 @@
 #include "tkv_crc32_device.h"
 #include "tkv_device_util.h"
 #include "tkv_engine.h"
+#include "tkv_scan.h"
 #include "tkv_wal_copy.h"
 #include "tkv_wal_device.h"
 #include "tkv_wal_fold.h"
@@ -284,65 +285,39 @@ __global__ __launch_bounds__(kEncThreads) void enc_emit(EncArgs a) {
 
 // ---- host side --------------------------------------------------------------------------------------
 
+// An entry of the read-back list, for its size alone: the list is four arrays of lng.cap entries each.
+struct LongRec {
+  std::uint32_t off[2], len, idx, crc;
+};
+
 // Per-device scratch, grown by doubling and kept between calls (guarded by mu).
-struct EncScratch {
-  std::mutex mu;
-  std::uint64_t cap_off = 0, cap_sum = 0, cap_tile = 0, cap_long = 0;
-  void* off = nullptr;    // record offsets (u64)
-  void* sums = nullptr;   // block sums of every scan level (u64)
-  void* tiles = nullptr;  // first and last record of every tile (2 x u32)
-  void* lng = nullptr;    // read-back list: off (u64), len, idx, crc (u32)
-  unsigned long long* cnt = nullptr;
-  std::uint64_t* h_res = nullptr;   // pinned, kEncHres words
-  std::uint64_t* d_hres = nullptr;  // device view of h_res
-  int ncu = 0;
-  ~EncScratch() {
-    (void)hipFree(off);
-    (void)hipFree(sums);
-    (void)hipFree(tiles);
-    (void)hipFree(lng);
-    (void)hipFree(cnt);
-    (void)hipHostFree(h_res);
-  }
+struct EncScratch : ScratchBase {
+  DeviceBuf off;    // record offsets (u64)
+  DeviceBuf sums;   // block sums of every scan level (u64)
+  DeviceBuf tiles;  // first and last record of every tile (2 x u32)
+  DeviceBuf lng;    // read-back list: off (u64), len, idx, crc (u32)
+  unsigned long long*& cnt = words;
 };
 
 std::atomic<int> g_enc_fused{1};
 // What the calling thread's last device encode did (tkv_debug_wal_encode_last).
 thread_local std::uint64_t g_enc_last[4] = {0, 0, 0, 0};
 
-int scratch(EncScratch** out) {
-  EncScratch* sp = nullptr;
-  if (int rc = per_device(&sp)) return rc;
-  std::lock_guard<std::mutex> lk(sp->mu);
-  if (!sp->cnt) {
-    sp->ncu = device_cu_count();
-    TKV_HIP_RC(hipHostMalloc(reinterpret_cast<void**>(&sp->h_res), kEncHres * sizeof(std::uint64_t), hipHostMallocDefault));
-    TKV_HIP_RC(hipHostGetDevicePointer(reinterpret_cast<void**>(&sp->d_hres), sp->h_res, 0));
-    TKV_HIP_RC(hipMalloc(reinterpret_cast<void**>(&sp->cnt), kCntWords * sizeof(unsigned long long)));
-  }
-  *out = sp;
-  return TKV_OK;
-}
-
 int encode_locked(EncScratch& s, EncArgs a, std::uint64_t cap, std::uint64_t* img_size, hipStream_t st) {
   const ScanPlan plan(a.n);
   const int levels = plan.levels;
-  const std::uint64_t* m = plan.m;
-  if (int rc = grow(&s.off, &s.cap_off, a.n, 8)) return rc;
-  if (int rc = grow(&s.sums, &s.cap_sum, plan.nsum, 8)) return rc;
-  a.off = static_cast<std::uint64_t*>(s.off);
+  std::uint64_t* sums = nullptr;
+  if (int rc = s.off.take(a.n, &a.off)) return rc;
+  if (int rc = s.sums.take(plan.nsum, &sums)) return rc;
   a.cnt = s.cnt;
   std::uint64_t* lv[kScanLevels + 1];
-  plan.place(a.off, static_cast<std::uint64_t*>(s.sums), lv);
+  plan.place(a.off, sums, lv);
   TKV_HIP_RC(hipMemsetAsync(s.cnt, 0, kCntWords * sizeof(unsigned long long), st));
   s.h_res[3] = 0;
-  hipLaunchKernelGGL(enc_scan, dim3(static_cast<unsigned>(m[1])), dim3(kScanThreads), 0, st, a, lv[1]);
-  for (int k = 1; k < levels; ++k)
-    hipLaunchKernelGGL(scan_level, dim3(static_cast<unsigned>(m[k + 1])), dim3(kScanThreads), 0, st, lv[k], m[k], lv[k + 1]);
+  hipLaunchKernelGGL(enc_scan, dim3(static_cast<unsigned>(plan.m[1])), dim3(kScanThreads), 0, st, a, lv[1]);
+  scan_up(plan, lv, st);
   hipLaunchKernelGGL(enc_publish, dim3(1), dim3(64), 0, st, lv[levels], s.cnt, s.d_hres);
-  TKV_HIP_RC(hipGetLastError());
-  TKV_HIP_RC(hipStreamSynchronize(st));
-  if (s.h_res[3] != 1) return set_error(TKV_IO_ERROR, "WAL encode: the size scan left no result");
+  if (int rc = s.wait(st, 3, 1, "WAL encode: the size scan left no result")) return rc;
   const std::uint64_t total = s.h_res[0], nlong = s.h_res[2];
   if (s.h_res[1]) return set_error(TKV_INVALID_ARGUMENT, "WAL encode: 18 + key_len + val_len does not fit u32");
   *img_size = total;
@@ -350,15 +325,14 @@ int encode_locked(EncScratch& s, EncArgs a, std::uint64_t cap, std::uint64_t* im
   if (!a.img) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
   a.total = total;
   a.ntiles = (total + kEncTile - 1u) / kEncTile;
-  if (int rc = grow(&s.tiles, &s.cap_tile, a.ntiles, 8)) return rc;
-  if (int rc = grow(&s.lng, &s.cap_long, nlong, 8 + 3 * 4)) return rc;
-  a.tile_first = static_cast<std::uint32_t*>(s.tiles);
-  a.l_off = static_cast<std::uint64_t*>(s.lng);
-  a.l_len = reinterpret_cast<std::uint32_t*>(a.l_off + s.cap_long);
-  a.l_idx = a.l_len + s.cap_long;
-  a.l_crc = a.l_idx + s.cap_long;
-  for (int k = levels - 2; k >= 1; --k)
-    hipLaunchKernelGGL(scan_add, dim3(blocks(m[k], kScanThreads)), dim3(kScanThreads), 0, st, lv[k], m[k], lv[k + 1]);
+  LongRec* lng = nullptr;
+  if (int rc = s.tiles.take(2u * a.ntiles, &a.tile_first)) return rc;
+  if (int rc = s.lng.take(nlong, &lng)) return rc;
+  a.l_off = reinterpret_cast<std::uint64_t*>(lng);
+  a.l_len = reinterpret_cast<std::uint32_t*>(a.l_off + s.lng.cap);
+  a.l_idx = a.l_len + s.lng.cap;
+  a.l_crc = a.l_idx + s.lng.cap;
+  scan_down(plan, lv, st, 1);  // (enc_finish adds lv[1] itself)
   hipLaunchKernelGGL(enc_finish, dim3(blocks(a.n, kScanThreads)), dim3(kScanThreads), 0, st, a,
                      levels > 1 ? lv[1] : static_cast<const std::uint64_t*>(nullptr));
   const std::uint64_t want = (a.ntiles + kEncWaves - 1u) / kEncWaves;
@@ -390,7 +364,7 @@ int wal_encode_device_impl(const std::uint8_t* d_keys, const std::uint64_t* d_ke
   const DeviceTables* tabs = device_tables(kAlgoCrc32);
   if (!tabs) return TKV_IO_ERROR;
   EncScratch* sp = nullptr;
-  if (int rc = scratch(&sp)) return rc;
+  if (int rc = per_device_scratch(&sp, kEncHres, kCntWords, false)) return rc;
   EncArgs a{};
   a.keys = d_keys;
   a.key_off = d_key_off;
