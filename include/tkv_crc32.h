@@ -803,6 +803,13 @@ void tkv_debug_memtable_geom(uint64_t out[4]);
  * bytes and equal in their first 8 to another such record), out[3] = scratch bytes the call asked for
  * (all 0 when it did not reach its end). */
 void tkv_debug_memtable_last(uint64_t out[4]);
+/* Which radix passes the calling thread's last tkv_memtable_build_device launched, over all its rounds
+ * (pass 0 = the 4 digit bits, 1-8 = the word's bytes from the lowest, 9-12 = the segment's bytes from the
+ * lowest): out[0] = OR of 1 << p for every pass one workgroup ran (a list of at most
+ * tkv_debug_memtable_geom's out[0] entries), out[1] = the same for passes run as histogram, scan and
+ * scatter, out[2] = passes run in the whole build, out[3] = the most levels a histogram scan had (0 when
+ * there was none). Cleared when a build starts and recorded on the host as the passes are launched. */
+void tkv_debug_memtable_passes(uint64_t out[4]);
 /* Phase times of the calling thread's last tkv_memtable_build_device that returned TKV_OK, in
  * milliseconds between device events on its stream: out_ms[0] = the check and the first round, out_ms[1]
  * = the later rounds, out_ms[2] = dedupe (the survivor scans), out_ms[3] = emit (columns, metadata, the

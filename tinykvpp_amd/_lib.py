@@ -100,6 +100,7 @@ SIGNATURES = {
                                   _vp, _u64] + [ctypes.POINTER(_u64)] * 3),
     "tkv_debug_memtable_geom": (None, [_vp]),
     "tkv_debug_memtable_last": (None, [_vp]),
+    "tkv_debug_memtable_passes": (None, [_vp]),
     "tkv_debug_memtable_phases": (_int, [_int, _vp]),
     "tkv_crc32c_update": (_int, [_u32, _vp, _sz, ctypes.POINTER(_u32)]),
     "tkv_crc32c_update_device": (_int, [_u32, _vp, _sz, _vp, _vp]),
@@ -149,7 +150,7 @@ OPTIONAL = {"tkv_build_id", "tkv_wal_index_device", "tkv_wal_index", "tkv_debug_
             "tkv_debug_sst_build_phases", "tkv_sst_scan_device", "tkv_sst_scan", "tkv_debug_sst_scan_parse",
             "tkv_debug_sst_scan_geometry", "tkv_debug_sst_scan_last", "tkv_debug_sst_scan_phases",
             "tkv_memtable_build_device", "tkv_memtable_build", "tkv_debug_memtable_geom", "tkv_debug_memtable_last",
-            "tkv_debug_memtable_phases"}
+            "tkv_debug_memtable_phases", "tkv_debug_memtable_passes"}
 
 _lib = None
 

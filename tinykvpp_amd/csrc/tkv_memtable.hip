@@ -454,6 +454,10 @@ struct MtScratch : ScratchBase {
 
 // What the calling thread's last device build did (tkv_debug_memtable_last).
 thread_local std::uint64_t g_mt_last[4] = {0, 0, 0, 0};
+// Which passes the calling thread's last device build launched (tkv_debug_memtable_passes): bit p of [0]
+// for a pass one workgroup ran, of [1] for one run as histogram, scan and scatter; [2] the passes run,
+// [3] the deepest histogram scan. Written by sort_list only.
+thread_local std::uint64_t g_mt_passes[4] = {0, 0, 0, 0};
 // Phase times of the calling thread's builds (tkv_debug_memtable_phases): device events at the phase
 // boundaries while g_mt_timing is set.
 thread_local int g_mt_timing = 0;
@@ -483,8 +487,11 @@ int sort_list(const List* l, int cur, std::uint64_t m, std::uint64_t diffw, std:
     if (pass_digit(p, diffw, diffx) == 0u) continue;
     if (nblk == 1) {
       hipLaunchKernelGGL(mt_pass<2>, dim3(1), dim3(kMtThreads), 0, st, l[cur], l[cur ^ 1], m, p, hist, 1u);
+      g_mt_passes[0] |= 1ull << p;
     } else {
       const ScanPlan plan(kMtBuckets * nblk);
+      g_mt_passes[1] |= 1ull << p;
+      g_mt_passes[3] = std::max<std::uint64_t>(g_mt_passes[3], static_cast<std::uint64_t>(plan.levels));
       std::uint64_t* lv[kScanLevels + 1];
       plan.place(hist, hsums, lv);
       const dim3 g(static_cast<unsigned>(nblk)), tb(kMtThreads);
@@ -493,6 +500,7 @@ int sort_list(const List* l, int cur, std::uint64_t m, std::uint64_t diffw, std:
       scan_rest(plan, lv, st);
       hipLaunchKernelGGL(mt_pass<1>, g, tb, 0, st, l[cur], l[cur ^ 1], m, p, hist, static_cast<std::uint32_t>(nblk));
     }
+    ++g_mt_passes[2];
     cur ^= 1;
   }
   return cur;
@@ -634,6 +642,7 @@ int build_locked(MtScratch& s, MtArgs a, const MemtableCall& c, hipStream_t st) 
 int memtable_build_device_impl(const MemtableCall& c, hipStream_t st) {
   for (auto& v : g_mt_last) v = 0;
   for (auto& v : g_mt_phase) v = 0;
+  for (auto& v : g_mt_passes) v = 0;
   MtScratch* sp = nullptr;
   if (int rc = per_device_scratch(&sp, kMtHres, kStWords, true)) return rc;
   MtArgs a{};
@@ -671,6 +680,10 @@ void tkv_debug_memtable_geom(uint64_t out[4]) {
 
 void tkv_debug_memtable_last(uint64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tkv::g_mt_last[i];
+}
+
+void tkv_debug_memtable_passes(uint64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = tkv::g_mt_passes[i];
 }
 
 int tkv_debug_memtable_phases(int enable, double out_ms[4]) {
