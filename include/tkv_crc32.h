@@ -583,6 +583,88 @@ int tkv_memtable_build(const uint8_t *h_keys, uint64_t keys_size,
                        uint64_t entry_cap,
                        uint64_t *n_entries, uint64_t *ikeys_size, uint64_t *first_bad);
 
+/* ---- SSTable merge: k-way merge of sorted runs, newest wins ----------------------- */
+
+#define TKV_SST_MERGE_DROP_TOMBSTONES 1u   /* a surviving tombstone is left out (the last level) */
+#define TKV_SST_MERGE_MAX_RUNS 64u
+#define TKV_SST_MERGE_NONE UINT64_MAX      /* *first_bad when nothing is bad */
+
+/* Compaction's merge: n_runs sorted runs of internal keys into one run without shadowed entries. The
+ * per-run arguments (d_keys, keys_size, d_key_off, d_key_len, d_val_off, d_val_len, n, val_bias) are HOST
+ * arrays of n_runs elements; the elements of the pointer arrays are device pointers (host pointers for
+ * tkv_sst_merge).
+ * Runs are given OLDEST FIRST. Run r holds n[r] entries; entry i has the internal key [d_keys[r] +
+ * key_off_r[i], + key_len_r[i]) and the value span (val_off_r[i], val_len_r[i]): exactly the columns
+ * tkv_sst_scan_device returns with both view flags, and the ones tkv_memtable_build_device returns.
+ * d_val_off / d_val_len may be NULL as a whole or per run: every value of that run is then empty, span
+ * (0, 0) plus the bias. VALUES ARE NEVER READ; keys are read but never copied.
+ * Keys: the user key of an entry is its internal key without the last 17 bytes (u64 seq | u64 timestamp |
+ * u8 tombstone). Sequence and timestamp are NOT interpreted. The tombstone is the last byte, != 0.
+ * Order: the memtable replay's: user keys as unsigned bytes, a prefix first. Each run must be ascending by
+ * user key, non-strictly: equal neighbours inside one run are allowed.
+ * Survivor: of all entries with one user key the one from the HIGHEST-NUMBERED RUN survives, and within
+ * that run the one with the highest index: the replay's "latest in input order" applied to the
+ * concatenation of the runs. It is NOT "highest sequence": skiplist::insert replaces the node of an equal
+ * user key whatever its seq (skiplist.hpp:201-242), so the entry written last is the one a reader of the
+ * reference would find, and a merge that looked at seq would disagree with the replay on the same records.
+ * Tombstone drop: with TKV_SST_MERGE_DROP_TOMBSTONES a survivor whose tombstone byte is non-zero is left
+ * out; it still shadows the older entries of its key. Without the flag it is kept with its value span as
+ * given.
+ * Outputs, each nullable and then skipped: the m = *n_entries survivors ascending; out_key_len[j] /
+ * out_val_len[j] copied; out_key_off[j] = (d_keys[r] - d_key_base) + key_off_r[i]; out_val_off[j] =
+ * val_bias[r] + val_off_r[i] (val_bias NULL: zeros); out_src[j] = r << 32 | i; *keys_bytes / *vals_bytes
+ * the sums of the survivors' lengths. The offsets are meant for the flush, tkv_sst_build_device with
+ * d_key_base, out_key_off, out_key_len, the value base, out_val_off, out_val_len and m: that call takes one
+ * base per arena and has no arena size. The result is unique, so two calls agree bit for bit.
+ * Sizing and overflow: m > entry_cap with any output column non-NULL: TKV_BUFFER_OVERFLOW with the three
+ * sizes set and nothing written (entry_cap 0 with all columns NULL is the sizing call, TKV_OK).
+ * TKV_CORRUPTED, found by a check pass (on the device in the device call), no output array written, the
+ * three sizes 0: *first_bad = the smallest r << 32 | i for which key_len < 17, or key_len >= 2^28, or
+ * key_off + key_len > keys_size[r], or entries i and i - 1 both pass these three checks and the user key of
+ * i is smaller than that of i - 1. Otherwise *first_bad = TKV_SST_MERGE_NONE.
+ * TKV_INVALID_ARGUMENT, before any device work and with nothing touched: n_runs > TKV_SST_MERGE_MAX_RUNS;
+ * unknown flag bits; NULL n_entries / keys_bytes / vals_bytes / first_bad; with n_runs > 0 NULL d_keys /
+ * keys_size / d_key_off / d_key_len / n, or a NULL element of d_keys / d_key_off / d_key_len for a run
+ * with n[r] > 0; d_val_len[r] without d_val_off[r]; some n[r] > 2^32 - 1 or the total N > 2^32 - 1;
+ * d_key_base NULL or above some d_keys[r] of a non-empty run while d_out_key_off is non-NULL.
+ * n_runs == 0 or N == 0: TKV_OK, sizes 0, *first_bad = TKV_SST_MERGE_NONE, nothing else touched. Empty
+ * runs among non-empty ones are fine.
+ * Reads: no byte outside [d_keys[r], d_keys[r] + keys_size[r]) is read, beyond the aligned 16-byte granule
+ * that holds a key byte (the replay's rule).
+ * The device call is synchronous on `stream` with TWO host synchronisations, whatever K, N and the key
+ * lengths: one for the verdict and the sizes (the kernels behind the check pass read the verdict on the
+ * device and do nothing on bad input, so the host need not wait in between), one at the end of the emit.
+ * With no usable GPU it returns TKV_IO_ERROR; a scratch allocation that fails returns TKV_OUT_OF_MEMORY
+ * (the scratch holds 41 bytes per input entry: two lists of 16-byte sort entries, the survivor scan and
+ * a flag; plus 16 bytes per workgroup tile of every round and 24 per 1024 entries for the scan's sums). No key byte crosses PCIe: only the run table,
+ * the tile map and a small pinned result block do. One GPU; K > 64 is refused. */
+int tkv_sst_merge_device(uint32_t n_runs,
+                         const uint8_t *const *d_keys, const uint64_t *keys_size,
+                         const uint64_t *const *d_key_off, const uint32_t *const *d_key_len,
+                         const uint64_t *const *d_val_off, const uint32_t *const *d_val_len,
+                         const uint64_t *n,
+                         const uint8_t *d_key_base, const uint64_t *val_bias, uint32_t flags,
+                         uint64_t *d_out_key_off, uint32_t *d_out_key_len,
+                         uint64_t *d_out_val_off, uint32_t *d_out_val_len, uint64_t *d_out_src,
+                         uint64_t entry_cap,
+                         uint64_t *n_entries, uint64_t *keys_bytes, uint64_t *vals_bytes, uint64_t *first_bad,
+                         void *stream);
+
+/* The same contract with every pointer in HOST memory: the runs validated on host threads, then
+ * neighbouring lists merged pairwise on host threads with a full-key comparator (the older side first on
+ * equal keys), then the same survivor rule and emit. It uses no GPU at all and is NOT a fallback of the
+ * device call. */
+int tkv_sst_merge(uint32_t n_runs,
+                  const uint8_t *const *h_keys, const uint64_t *keys_size,
+                  const uint64_t *const *h_key_off, const uint32_t *const *h_key_len,
+                  const uint64_t *const *h_val_off, const uint32_t *const *h_val_len,
+                  const uint64_t *n,
+                  const uint8_t *h_key_base, const uint64_t *val_bias, uint32_t flags,
+                  uint64_t *h_out_key_off, uint32_t *h_out_key_len,
+                  uint64_t *h_out_val_off, uint32_t *h_out_val_len, uint64_t *h_out_src,
+                  uint64_t entry_cap,
+                  uint64_t *n_entries, uint64_t *keys_bytes, uint64_t *vals_bytes, uint64_t *first_bad);
+
 /* ---- CRC-32C (Castagnoli) — SURVEY.md §8f rank 4 ------------------------------------------------ */
 
 /* Same engine and kernels with the tables of the Castagnoli polynomial (reflected 0x82F63B78,
@@ -816,6 +898,19 @@ void tkv_debug_memtable_passes(uint64_t out[4]);
  * arena; with the host's read of the sizes in front). Switch and return value as
  * tkv_debug_sst_build_phases. */
 int tkv_debug_memtable_phases(int enable, double out_ms[4]);
+
+/* Outputs one workgroup of tkv_sst_merge_device's merge rounds produces (its tile). Tests place their
+ * edges around it. */
+uint64_t tkv_debug_sst_merge_tile(void);
+/* What the calling thread's last tkv_sst_merge_device did: out[0] = N (input entries), out[1] = merge
+ * rounds launched (ceil(log2) of the non-empty runs), out[2] = workgroup tiles of the last round, out[3] =
+ * scratch bytes the call asked for (all 0 when it did not reach its end). */
+void tkv_debug_sst_merge_last(uint64_t out[4]);
+/* Phase times of the calling thread's last tkv_sst_merge_device that returned TKV_OK, in milliseconds
+ * between device events on its stream: out_ms[0] = the check pass and the sort entries, out_ms[1] = the
+ * merge rounds, out_ms[2] = ties, tombstone drop and the survivor scan, out_ms[3] = emit (with the host's
+ * read of the verdict and the sizes in front). Switch and return value as tkv_debug_sst_build_phases. */
+int tkv_debug_sst_merge_phases(int enable, double out_ms[4]);
 
 #ifdef __cplusplus
 }

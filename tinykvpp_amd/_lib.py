@@ -102,6 +102,11 @@ SIGNATURES = {
     "tkv_debug_memtable_last": (None, [_vp]),
     "tkv_debug_memtable_passes": (None, [_vp]),
     "tkv_debug_memtable_phases": (_int, [_int, _vp]),
+    "tkv_sst_merge_device": (_int, [_u32] + [_vp] * 9 + [_u32] + [_vp] * 5 + [_u64] + [ctypes.POINTER(_u64)] * 4 + [_vp]),
+    "tkv_sst_merge": (_int, [_u32] + [_vp] * 9 + [_u32] + [_vp] * 5 + [_u64] + [ctypes.POINTER(_u64)] * 4),
+    "tkv_debug_sst_merge_tile": (_u64, []),
+    "tkv_debug_sst_merge_last": (None, [_vp]),
+    "tkv_debug_sst_merge_phases": (_int, [_int, _vp]),
     "tkv_crc32c_update": (_int, [_u32, _vp, _sz, ctypes.POINTER(_u32)]),
     "tkv_crc32c_update_device": (_int, [_u32, _vp, _sz, _vp, _vp]),
     "tkv_crc32c_batch_device": (_int, [_u8p, _vp, _vp, _vp, _vp, _u64, _vp]),
@@ -150,7 +155,8 @@ OPTIONAL = {"tkv_build_id", "tkv_wal_index_device", "tkv_wal_index", "tkv_debug_
             "tkv_debug_sst_build_phases", "tkv_sst_scan_device", "tkv_sst_scan", "tkv_debug_sst_scan_parse",
             "tkv_debug_sst_scan_geometry", "tkv_debug_sst_scan_last", "tkv_debug_sst_scan_phases",
             "tkv_memtable_build_device", "tkv_memtable_build", "tkv_debug_memtable_geom", "tkv_debug_memtable_last",
-            "tkv_debug_memtable_phases", "tkv_debug_memtable_passes"}
+            "tkv_debug_memtable_phases", "tkv_debug_memtable_passes", "tkv_sst_merge_device", "tkv_sst_merge",
+            "tkv_debug_sst_merge_tile", "tkv_debug_sst_merge_last", "tkv_debug_sst_merge_phases"}
 
 _lib = None
 

@@ -91,4 +91,33 @@ struct MemtableCall {
 // checked by the caller).
 int memtable_build_device_impl(const MemtableCall& c, hipStream_t st);
 
+// The arguments of tkv_sst_merge[_device] (include/tkv_crc32.h "SSTable merge"): the per-run arrays are
+// host arrays of n_runs elements in both calls.
+struct SstMergeCall {
+  std::uint32_t n_runs;
+  const std::uint8_t* const* keys;
+  const std::uint64_t* keys_size;
+  const std::uint64_t* const* key_off;
+  const std::uint32_t* const* key_len;
+  const std::uint64_t* const* val_off;  // nullable, and every element nullable
+  const std::uint32_t* const* val_len;
+  const std::uint64_t* n;
+  const std::uint8_t* key_base;
+  const std::uint64_t* val_bias;  // nullable: zeros
+  std::uint32_t flags;
+  std::uint64_t* out_key_off;
+  std::uint32_t* out_key_len;
+  std::uint64_t* out_val_off;
+  std::uint32_t* out_val_len;
+  std::uint64_t* out_src;
+  std::uint64_t entry_cap;
+  std::uint64_t *n_entries, *keys_bytes, *vals_bytes, *first_bad;
+};
+
+// tkv_sst_merge.hip: the k-way merge on `st` (synchronous): the check pass with the sort entries, the
+// merge-path rounds, the ties and the survivor scan, the host's corrupted / overflow decision from a pinned
+// result, the columns. Arguments and results are tkv_sst_merge_device's (the argument checks made and
+// 1 <= N <= 2^32 - 1 by the caller).
+int sst_merge_device_impl(const SstMergeCall& c, hipStream_t st);
+
 }  // namespace tkv

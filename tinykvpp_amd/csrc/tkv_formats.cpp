@@ -1448,3 +1448,181 @@ int tkv_memtable_build(const uint8_t* h_keys, uint64_t keys_size, const uint64_t
 }
 
 }  // extern "C"
+
+namespace {
+// ---- SSTable merge (compaction's k-way merge of sorted runs; include/tkv_crc32.h "SSTable merge") ----
+
+constexpr std::uint64_t kMergeNone = TKV_SST_MERGE_NONE;
+
+// The checks both entry points make before any work; *total = N.
+int sst_merge_check(const SstMergeCall& c, std::uint64_t* total) {
+  *total = 0;
+  if (!ptr_ok(c.n_entries) || !ptr_ok(c.keys_bytes) || !ptr_ok(c.vals_bytes) || !ptr_ok(c.first_bad))
+    return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  if (c.n_runs > TKV_SST_MERGE_MAX_RUNS) return set_error(TKV_INVALID_ARGUMENT, "sst merge: more than 64 runs");
+  if (c.flags & ~TKV_SST_MERGE_DROP_TOMBSTONES) return set_error(TKV_INVALID_ARGUMENT, "sst merge: unknown flag bits");
+  if (c.n_runs == 0) return TKV_OK;
+  if (!ptr_ok(c.keys) || !ptr_ok(c.keys_size) || !ptr_ok(c.key_off) || !ptr_ok(c.key_len) || !ptr_ok(c.n))
+    return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  std::uint64_t sum = 0;
+  for (std::uint32_t r = 0; r < c.n_runs; ++r) {
+    if (c.n[r] > 0xFFFFFFFFull) return set_error(TKV_INVALID_ARGUMENT, "sst merge: more than 2^32 - 1 entries in a run");
+    sum += c.n[r];
+    if (sum > 0xFFFFFFFFull) return set_error(TKV_INVALID_ARGUMENT, "sst merge: more than 2^32 - 1 entries");
+    if (ptr_ok(c.val_len) && ptr_ok(c.val_len[r]) && !(ptr_ok(c.val_off) && ptr_ok(c.val_off[r])))
+      return set_error(TKV_INVALID_ARGUMENT, "sst merge: val_len without val_off");
+    if (c.n[r] == 0) continue;
+    if (!ptr_ok(c.keys[r]) || !ptr_ok(c.key_off[r]) || !ptr_ok(c.key_len[r])) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+    if (ptr_ok(c.out_key_off) && (!ptr_ok(c.key_base) || c.key_base > c.keys[r]))
+      return set_error(TKV_INVALID_ARGUMENT, "sst merge: key_base is not below every run's keys");
+  }
+  *total = sum;
+  return TKV_OK;
+}
+
+// N == 0 (both entry points).
+int sst_merge_empty(const SstMergeCall& c) {
+  *c.n_entries = *c.keys_bytes = *c.vals_bytes = 0;
+  *c.first_bad = kMergeNone;
+  return TKV_OK;
+}
+
+int sst_merge_host(const SstMergeCall& c) {
+  std::uint64_t total = 0;
+  if (int rc = sst_merge_check(c, &total)) return rc;
+  if (total == 0) return sst_merge_empty(c);
+  const std::uint32_t K = c.n_runs;
+  auto span_ok = [&](std::uint32_t r, std::uint64_t i) {
+    const std::uint64_t ko = c.key_off[r][i];
+    const std::uint32_t kl = c.key_len[r][i];
+    return kl >= kMtMeta && kl < kMtMaxIkey && ko <= c.keys_size[r] && kl <= c.keys_size[r] - ko;
+  };
+  // simd_comparator's order on the user keys: unsigned bytes, a prefix first
+  auto cmp = [&](std::uint64_t x, std::uint64_t y) {
+    const std::uint32_t rx = static_cast<std::uint32_t>(x >> 32), ry = static_cast<std::uint32_t>(y >> 32);
+    const std::uint64_t ix = x & 0xFFFFFFFFull, iy = y & 0xFFFFFFFFull;
+    const std::uint32_t lx = c.key_len[rx][ix] - kMtMeta, ly = c.key_len[ry][iy] - kMtMeta;
+    const std::uint32_t m = std::min(lx, ly);
+    const int v = m ? std::memcmp(c.keys[rx] + c.key_off[rx][ix], c.keys[ry] + c.key_off[ry][iy], m) : 0;
+    return v ? v : (lx < ly ? -1 : lx > ly ? 1 : 0);
+  };
+  // validate: every run's smallest bad index on host threads, the runs in order
+  std::vector<std::uint64_t> bad(K, kMergeNone);
+  {
+    std::vector<std::thread> th;
+    const unsigned nt = total >= (1u << 14) ? host_threads() : 1u;
+    std::atomic<std::uint32_t> next{0};
+    auto work = [&] {
+      for (std::uint32_t r = next++; r < K; r = next++) {
+        bool prev_ok = false;
+        for (std::uint64_t i = 0; i < c.n[r]; ++i) {
+          const bool ok = span_ok(r, i);
+          const std::uint64_t id = (static_cast<std::uint64_t>(r) << 32) | i;
+          if (!ok || (prev_ok && cmp(id, id - 1) < 0)) {
+            bad[r] = id;
+            break;
+          }
+          prev_ok = ok;
+        }
+      }
+    };
+    for (unsigned t = 1; t < std::min<unsigned>(nt, K); ++t) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+  }
+  *c.n_entries = *c.keys_bytes = *c.vals_bytes = 0;
+  *c.first_bad = *std::min_element(bad.begin(), bad.end());
+  if (*c.first_bad != kMergeNone) return set_error(TKV_CORRUPTED, "sst merge: a key span is out of bounds or a run is not ascending");
+  // the lists of r << 32 | i, neighbouring lists merged pairwise on host threads, the older side first
+  // on equal keys
+  std::vector<std::uint64_t> cur(total), nxt(total);
+  std::vector<std::uint64_t> cut{0};
+  for (std::uint32_t r = 0; r < K; ++r) {
+    if (c.n[r] == 0) continue;
+    const std::uint64_t at = cut.back();
+    for (std::uint64_t i = 0; i < c.n[r]; ++i) cur[at + i] = (static_cast<std::uint64_t>(r) << 32) | i;
+    cut.push_back(at + c.n[r]);
+  }
+  auto less = [&](std::uint64_t x, std::uint64_t y) { return cmp(x, y) < 0; };
+  while (cut.size() > 2) {
+    std::vector<std::uint64_t> ncut{0};
+    std::vector<std::thread> th;
+    for (std::size_t p = 0; p + 1 < cut.size(); p += 2) {
+      const std::uint64_t s0 = cut[p], s1 = cut[p + 1], s2 = p + 2 < cut.size() ? cut[p + 2] : s1;
+      auto job = [&, s0, s1, s2] {
+        std::merge(cur.begin() + s0, cur.begin() + s1, cur.begin() + s1, cur.begin() + s2, nxt.begin() + s0, less);
+      };
+      if (total >= (1u << 14)) th.emplace_back(job);
+      else job();
+      ncut.push_back(s2);
+    }
+    for (auto& t : th) t.join();
+    cur.swap(nxt);
+    cut.swap(ncut);
+  }
+  // the last of every group of equal keys, without the tombstones under the flag
+  const bool drop = (c.flags & TKV_SST_MERGE_DROP_TOMBSTONES) != 0;
+  std::vector<std::uint64_t> sv;
+  std::uint64_t kb = 0, vb = 0;
+  for (std::uint64_t j = 0; j < total; ++j) {
+    if (j + 1 < total && cmp(cur[j], cur[j + 1]) == 0) continue;
+    const std::uint32_t r = static_cast<std::uint32_t>(cur[j] >> 32);
+    const std::uint64_t i = cur[j] & 0xFFFFFFFFull;
+    const std::uint32_t kl = c.key_len[r][i];
+    if (drop && c.keys[r][c.key_off[r][i] + kl - 1u] != 0) continue;
+    sv.push_back(cur[j]);
+    kb += kl;
+    if (ptr_ok(c.val_len) && ptr_ok(c.val_len[r])) vb += c.val_len[r][i];
+  }
+  const std::uint64_t m = sv.size();
+  *c.n_entries = m;
+  *c.keys_bytes = kb;
+  *c.vals_bytes = vb;
+  const bool want_cols = ptr_ok(c.out_key_off) || ptr_ok(c.out_key_len) || ptr_ok(c.out_val_off) || ptr_ok(c.out_val_len) || ptr_ok(c.out_src);
+  if (want_cols && m > c.entry_cap) return set_error(TKV_BUFFER_OVERFLOW, "sst merge: the entries do not fit");
+  if (!want_cols) return TKV_OK;
+  parallel_for(m, [&](std::uint64_t e) {
+    const std::uint32_t r = static_cast<std::uint32_t>(sv[e] >> 32);
+    const std::uint64_t i = sv[e] & 0xFFFFFFFFull;
+    if (ptr_ok(c.out_key_off)) c.out_key_off[e] = static_cast<std::uint64_t>(c.keys[r] - c.key_base) + c.key_off[r][i];
+    if (ptr_ok(c.out_key_len)) c.out_key_len[e] = c.key_len[r][i];
+    const std::uint64_t bias = ptr_ok(c.val_bias) ? c.val_bias[r] : 0u;
+    if (ptr_ok(c.out_val_off)) c.out_val_off[e] = bias + (ptr_ok(c.val_off) && ptr_ok(c.val_off[r]) ? c.val_off[r][i] : 0u);
+    if (ptr_ok(c.out_val_len)) c.out_val_len[e] = ptr_ok(c.val_len) && ptr_ok(c.val_len[r]) ? c.val_len[r][i] : 0u;
+    if (ptr_ok(c.out_src)) c.out_src[e] = sv[e];
+  });
+  return TKV_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tkv_sst_merge_device(uint32_t n_runs, const uint8_t* const* d_keys, const uint64_t* keys_size,
+                         const uint64_t* const* d_key_off, const uint32_t* const* d_key_len,
+                         const uint64_t* const* d_val_off, const uint32_t* const* d_val_len, const uint64_t* n,
+                         const uint8_t* d_key_base, const uint64_t* val_bias, uint32_t flags, uint64_t* d_out_key_off,
+                         uint32_t* d_out_key_len, uint64_t* d_out_val_off, uint32_t* d_out_val_len, uint64_t* d_out_src,
+                         uint64_t entry_cap, uint64_t* n_entries, uint64_t* keys_bytes, uint64_t* vals_bytes,
+                         uint64_t* first_bad, void* stream) {
+  const SstMergeCall c{n_runs, d_keys, keys_size, d_key_off, d_key_len, d_val_off, d_val_len, n, d_key_base, val_bias, flags,
+                       d_out_key_off, d_out_key_len, d_out_val_off, d_out_val_len, d_out_src, entry_cap,
+                       n_entries, keys_bytes, vals_bytes, first_bad};
+  std::uint64_t total = 0;
+  if (int rc = sst_merge_check(c, &total)) return rc;
+  if (total == 0) return sst_merge_empty(c);
+  return sst_merge_device_impl(c, static_cast<hipStream_t>(stream));
+}
+
+int tkv_sst_merge(uint32_t n_runs, const uint8_t* const* h_keys, const uint64_t* keys_size,
+                  const uint64_t* const* h_key_off, const uint32_t* const* h_key_len, const uint64_t* const* h_val_off,
+                  const uint32_t* const* h_val_len, const uint64_t* n, const uint8_t* h_key_base, const uint64_t* val_bias,
+                  uint32_t flags, uint64_t* h_out_key_off, uint32_t* h_out_key_len, uint64_t* h_out_val_off,
+                  uint32_t* h_out_val_len, uint64_t* h_out_src, uint64_t entry_cap, uint64_t* n_entries,
+                  uint64_t* keys_bytes, uint64_t* vals_bytes, uint64_t* first_bad) {
+  const SstMergeCall c{n_runs, h_keys, keys_size, h_key_off, h_key_len, h_val_off, h_val_len, n, h_key_base, val_bias, flags,
+                       h_out_key_off, h_out_key_len, h_out_val_off, h_out_val_len, h_out_src, entry_cap,
+                       n_entries, keys_bytes, vals_bytes, first_bad};
+  return sst_merge_host(c);
+}
+
+}  // extern "C"

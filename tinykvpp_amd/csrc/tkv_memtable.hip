@@ -41,6 +41,7 @@
 #include "tkv_crc32_device.h"
 #include "tkv_device_util.h"
 #include "tkv_engine.h"
+#include "tkv_key_word.h"
 #include "tkv_memtable_layout.h"
 #include "tkv_scan.h"
 #include "tkv_wal_copy.h"
@@ -136,19 +137,7 @@ __device__ __forceinline__ void fold_bits(unsigned long long* st, bool on, std::
   }
 }
 
-// Key bytes [addr, addr + min(rem, 8)) big-endian, zero-padded: aligned dwords that hold a byte of them,
-// shifted together (v_alignbyte); bytes of those dwords outside the span are masked away.
-__device__ __forceinline__ std::uint64_t load_word(std::uintptr_t addr, std::uint64_t rem) {
-  const std::uint32_t take = rem < kMtWordBytes ? static_cast<std::uint32_t>(rem) : kMtWordBytes;
-  if (take == 0) return 0;
-  const std::uintptr_t e = addr + take, a0 = addr & ~static_cast<std::uintptr_t>(3);
-  const std::uint32_t sh = static_cast<std::uint32_t>(addr & 3u);
-  const std::uint32_t w0 = ld4(a0, addr, e), w1 = ld4(a0 + 4u, addr, e), w2 = ld4(a0 + 8u, addr, e);
-  const std::uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, sh), hi = __builtin_amdgcn_alignbyte(w2, w1, sh);
-  std::uint64_t v = (static_cast<std::uint64_t>(hi) << 32) | lo;
-  if (take < 8u) v &= (1ull << (8u * take)) - 1ull;
-  return __builtin_bswap64(v);
-}
+// (load_word, the comparison word's key read: tkv_key_word.h)
 
 // The 8 bits pass p sorts by (p = 0: the digit's 4), and whether they differ anywhere in the list.
 __host__ __device__ inline std::uint32_t pass_digit(int p, std::uint64_t kw, std::uint64_t kx) {

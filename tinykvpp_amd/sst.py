@@ -413,3 +413,198 @@ def scan(file, key_views=False, val_views=False):
     return _scan(load_library().tkv_sst_scan, ctypes.c_void_p(buf.ctypes.data) if buf.size else None, buf.size, flags,
                  lambda count, kind: np.empty(count, kinds[kind]),
                  lambda a: ctypes.c_void_p(a.ctypes.data) if a.size else None, buf, ())
+
+
+# ---- merge: k-way merge of sorted runs, newest wins (include/tkv_crc32.h "SSTable merge") -------------
+MERGE_DROP_TOMBSTONES = 1
+MERGE_MAX_RUNS = 64
+MERGE_NONE = 2**64 - 1
+
+
+class MergeCorrupted(ValueError):
+    """A run the merge rejects: entry ``index`` of run ``run`` has a key span that does not hold (shorter
+    than the 17 metadata bytes, 2^28 bytes or more, past its arena) or a user key below the one in front of it."""
+
+    def __init__(self, run, index):
+        self.run, self.index = run, index
+        super().__init__(f"entry {index} of run {run} has a bad key span or is out of order")
+
+
+class MergedRun:
+    """What merge_device / merge return: one entry per surviving user key, ascending. ``key_off`` /
+    ``val_off`` count from the addresses ``key_base`` / ``val_base`` (the lowest key / value arena among the
+    runs; ``keys`` / ``vals`` are those arenas), ``key_len`` / ``val_len`` are the entries' own, ``src`` =
+    run << 32 | index names the surviving entry. ``arenas`` keeps every input arena alive."""
+
+    __slots__ = ("keys", "vals", "key_base", "val_base", "key_off", "key_len", "val_off", "val_len", "src", "n_entries",
+                 "keys_bytes", "vals_bytes", "arenas")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def entries(self):
+        """[(ikey, value)] as bytes, read through the bases and offsets as the flush reads them (tests and
+        small runs)."""
+        def host(t):
+            return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+
+        def addr(t):
+            return t.data_ptr() if hasattr(t, "data_ptr") else t.ctypes.data
+        held = [(addr(t), host(t).view(np.uint8).tobytes()) for t in self.arenas]
+
+        def read(at, ln):
+            if ln == 0:
+                return b""
+            for base, raw in held:
+                if base <= at and at + ln <= base + len(raw):
+                    return raw[at - base:at - base + ln]
+            raise ValueError("a span lies in no input arena")
+        ko, vo = host(self.key_off).view(np.uint64), host(self.val_off).view(np.uint64)
+        kl, vl = host(self.key_len).view(np.uint32), host(self.val_len).view(np.uint32)
+        return [(read(self.key_base + int(ko[j]), int(kl[j])), read(self.val_base + int(vo[j]), int(vl[j])))
+                for j in range(self.n_entries)]
+
+    def flush(self, target_block_size=4096, out=None, stream=None):
+        """The run as an SSTable file image: build_device straight through the two bases for a device run;
+        a host run gathers its entries first (build takes one arena of each kind). A run without an entry
+        (every survivor a dropped tombstone) raises: the flush refuses an empty table."""
+        if self.n_entries == 0:
+            raise ValueError("nothing survives the merge: an SSTable holds at least one entry")
+        if isinstance(self.key_off, np.ndarray):
+            return build(self.entries(), target_block_size=target_block_size)
+        return build_device(self.keys, self.key_off, self.key_len, self.vals, self.val_off, self.val_len,
+                            target_block_size=target_block_size, out=out, stream=stream)
+
+
+def _run_columns(run):
+    """(keys, key_off, key_len, vals, val_off, val_len) of a ScannedTable, a MemtableRun or such a tuple."""
+    if isinstance(run, ScannedTable):
+        return run.keys, run.key_off, run.key_len, run.vals, run.val_off, run.val_len
+    if hasattr(run, "ikeys"):
+        return run.ikeys, run.ikey_off, run.ikey_len, run.vals, run.val_off, run.val_len
+    keys, key_off, key_len, vals, val_off, val_len = run
+    return keys, key_off, key_len, vals, val_off, val_len
+
+
+def _merge(fn, cols, addr, count, alloc, ptr, drop_tombstones, tail, spare):
+    """The sizing call, then the merge into freshly allocated columns. ``addr(t)`` / ``count(t)`` give an
+    array's address and element count, ``alloc(count, kind)`` makes one, ``ptr`` its address or None,
+    ``spare()`` a one-byte arena for a merge without a value arena."""
+    from ._lib import BUFFER_OVERFLOW
+    K = len(cols)
+    if K > MERGE_MAX_RUNS:
+        raise ValueError(f"{K} runs: a merge takes at most {MERGE_MAX_RUNS}")
+    n = [count(c[2]) for c in cols]
+
+    def has(t):
+        return t is not None and count(t) > 0
+    key_arenas = [c[0] for c, k in zip(cols, n) if k and has(c[0])]
+    val_arenas = [c[3] for c, k in zip(cols, n) if k and has(c[3])]
+    keys = min(key_arenas, key=addr) if key_arenas else None
+    vals = min(val_arenas, key=addr) if val_arenas else spare()
+    key_base, val_base = addr(keys) if keys is not None else 0, addr(vals)
+
+    def table(ctype, values):
+        return (ctype * max(K, 1))(*values)
+    vp = ctypes.c_void_p
+    a_keys = table(vp, [addr(c[0]) if has(c[0]) else None for c in cols])
+    a_size = table(ctypes.c_uint64, [count(c[0]) if c[0] is not None else 0 for c in cols])
+    a_koff = table(vp, [addr(c[1]) if has(c[1]) else None for c in cols])
+    a_klen = table(vp, [addr(c[2]) if has(c[2]) else None for c in cols])
+    a_voff = table(vp, [addr(c[4]) if has(c[4]) and has(c[5]) else None for c in cols])
+    a_vlen = table(vp, [addr(c[5]) if has(c[4]) and has(c[5]) else None for c in cols])
+    a_n = table(ctypes.c_uint64, n)
+    a_bias = table(ctypes.c_uint64, [addr(c[3]) - val_base if k and has(c[3]) else 0 for c, k in zip(cols, n)])
+    res = [ctypes.c_uint64(0) for _ in range(4)]  # n_entries, keys_bytes, vals_bytes, first_bad
+    flags = MERGE_DROP_TOMBSTONES if drop_tombstones else 0
+
+    def call(out, cap):
+        rc = fn(K, a_keys, a_size, a_koff, a_klen, a_voff, a_vlen, a_n, vp(key_base) if key_base else None, a_bias, flags,
+                *[ptr(t) for t in out], cap, *[ctypes.byref(r) for r in res], *tail)
+        if rc == CORRUPTED:
+            raise MergeCorrupted(res[3].value >> 32, res[3].value & 0xFFFFFFFF)
+        return rc
+    rc = call([None] * 5, 0)  # the sizing call
+    if rc not in (OK, BUFFER_OVERFLOW):
+        check(rc)
+    m = res[0].value
+    out = [alloc(m, k) for k in ("u64", "u32", "u64", "u32", "u64")]  # key_off, key_len, val_off, val_len, src
+    if m:
+        check(call(out, m))
+    return MergedRun(keys=keys, vals=vals, key_base=key_base, val_base=val_base, key_off=out[0], key_len=out[1],
+                     val_off=out[2], val_len=out[3], src=out[4], n_entries=m, keys_bytes=res[1].value,
+                     vals_bytes=res[2].value,
+                     arenas=[t for c in cols for t in (c[0], c[3]) if has(t)])
+
+
+def merge_device(runs, drop_tombstones=False, stream=None):
+    """The k-way merge of sorted runs held on the device (tkv_sst_merge_device). ``runs`` is a list, OLDEST
+    FIRST, of ScannedTables scanned with both view flags, of MemtableRuns, or of (keys, key_off, key_len,
+    vals, val_off, val_len) tuples of CUDA tensors (uint8 arenas, int64 offsets, int32 lengths; vals,
+    val_off and val_len may be None). Of all entries with one user key the one from the last run survives;
+    ``drop_tombstones`` leaves surviving tombstones out (the last level only). Picks the lowest arena
+    addresses as the bases, makes the sizing call, then the merge. Returns a MergedRun of CUDA tensors
+    (key_off / val_off / src int64, key_len / val_len int32, u32 / u64 values). A bad run raises
+    MergeCorrupted. Synchronous on ``stream``."""
+    import torch
+    from .crc32 import _check_data, _check_vec, _launch_stream
+    cols = [_run_columns(r) for r in runs]
+    dev = next((c[2].device for c in cols), torch.device("cuda", torch.cuda.current_device()))
+    for keys, key_off, key_len, vals, val_off, val_len in cols:
+        n = key_len.numel()
+        if keys.dtype != torch.uint8:
+            raise ValueError("keys must be a uint8 tensor")
+        _check_data(keys)
+        _check_vec("key_off", key_off, torch.int64, n, dev)
+        _check_vec("key_len", key_len, torch.int32, n, dev)
+        if val_len is not None:
+            if val_off is None:
+                raise ValueError("val_len needs val_off")
+            _check_vec("val_off", val_off, torch.int64, n, dev)
+            _check_vec("val_len", val_len, torch.int32, n, dev)
+        if vals is not None:
+            _check_vec("vals", vals, torch.uint8, 0, dev)
+    other = stream is not None and stream != torch.cuda.current_stream(dev)
+    kinds = {"u8": torch.uint8, "u64": torch.int64, "u32": torch.int32}
+
+    def alloc(count, kind):
+        t = torch.empty(count, dtype=kinds[kind], device=dev)
+        if other:
+            t.record_stream(stream)
+        return t
+    return _merge(load_library().tkv_sst_merge_device, cols, lambda t: t.data_ptr(), lambda t: t.numel(), alloc,
+                  lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None, drop_tombstones,
+                  (_launch_stream(stream, dev),), lambda: alloc(1, "u8"))
+
+
+def merge(runs, drop_tombstones=False):
+    """The same on the host (tkv_sst_merge: host threads, no GPU): runs of numpy arrays (uint8 arenas,
+    uint64 offsets, uint32 lengths). Returns a MergedRun of numpy arrays."""
+    cols = []
+    for run in runs:
+        keys, key_off, key_len, vals, val_off, val_len = _run_columns(run)
+
+        def arr(a, dt):
+            return None if a is None else np.ascontiguousarray(a, dtype=dt)
+        cols.append((arr(keys, np.uint8), arr(key_off, np.uint64), arr(key_len, np.uint32), arr(vals, np.uint8),
+                     arr(val_off, np.uint64), arr(val_len, np.uint32)))
+    kinds = {"u8": np.uint8, "u64": np.uint64, "u32": np.uint32}
+    return _merge(load_library().tkv_sst_merge, cols, lambda a: a.ctypes.data, lambda a: a.size,
+                  lambda count, kind: np.empty(count, kinds[kind]),
+                  lambda a: ctypes.c_void_p(a.ctypes.data) if a is not None and a.size else None, drop_tombstones, (),
+                  lambda: np.zeros(1, np.uint8))
+
+
+def compact_device(files, target_block_size=4096, drop_tombstones=False, stream=None):
+    """Compaction on the device: scan_device of every file image (OLDEST FIRST, both arenas as views),
+    merge_device, and the flush of the merged run. Returns the BuiltTable of the new file. Only a compaction
+    into the last level may drop tombstones; one that leaves no entry raises ValueError."""
+    runs = [scan_device(f, key_views=True, val_views=True, stream=stream) for f in files]
+    return merge_device(runs, drop_tombstones=drop_tombstones, stream=stream).flush(target_block_size, stream=stream)
+
+
+def compact(files, target_block_size=4096, drop_tombstones=False):
+    """The same through the host calls (scan, merge, build)."""
+    runs = [scan(f, key_views=True, val_views=True) for f in files]
+    return merge(runs, drop_tombstones=drop_tombstones).flush(target_block_size)
