@@ -13,9 +13,14 @@
 //    threads with its compare-exchange minimum for first_bad (one caller's image has two bad records
 //    in different threads' ranges), then the threaded scatter of the columns and the two arenas;
 //  * the host WAL encode layout (tkv_debug_wal_encode_layout) of the same batches, records written
-//    on host threads into one image.
-// Results are checked against a sequential walk, a sequential decode and layout written here, and the
-// test oracle (oracle/crc32_oracle.c, linked into this test only). Prints ALL PASSED.
+//    on host threads into one image;
+//  * the host memtable replay (tkv_memtable_build) on 20 000 records per caller: the stable sort as
+//    chunks on host threads and pairwise merges, one width behind the other;
+//  * the host SSTable merge (tkv_sst_merge) on 4 runs of more than 2^14 entries in all per caller: the
+//    per-run validation and the pairwise merge rounds on host threads.
+// Results are checked against a sequential walk, a sequential decode and layout written here, the serial
+// replay and insertion merge of runs_reference.h, and the test oracle (oracle/crc32_oracle.c, linked into
+// this test only). Prints ALL PASSED.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -23,6 +28,7 @@
 #include <thread>
 #include <vector>
 
+#include "runs_reference.h"
 #include "tkv_crc32.h"
 
 extern "C" {
@@ -352,6 +358,72 @@ void check_wal_encode_layout() {
   for (auto& x : th) x.join();
 }
 
+// ---- tkv_memtable_build (20 000 records: the sort's chunks and pairwise merges on host threads) ------
+void check_memtable_build() {
+  std::vector<mt_ref::Case> cases;
+  std::vector<std::vector<uint32_t>> want;  // the surviving records in key order
+  for (int t = 0; t < 4; ++t) {
+    cases.push_back(mt_ref::make_case(1002 + t, 20000, 20000));  // (1005: keys as overlapping views)
+    want.push_back(mt_ref::replay(cases.back()));
+  }
+  std::vector<std::thread> th;
+  for (int t = 0; t < 4; ++t)
+    th.emplace_back([&, t] {
+      const mt_ref::Case& c = cases[t];
+      const uint64_t n = c.klen.size();
+      for (int rep = 0; rep < 2; ++rep) {
+        std::vector<uint32_t> src(n, 0xA5A5A5A5u);
+        std::vector<uint64_t> ikey_off(n);
+        uint64_t m = 0, size = 0, bad = 0;
+        const int rc = tkv_memtable_build(c.keys.data(), c.keys.size(), c.koff.data(), c.klen.data(), c.voff.data(),
+                                          c.vlen.data(), c.op.data(), c.tomb.data(), c.seq.data(), n, c.ts, nullptr, 0,
+                                          ikey_off.data(), nullptr, nullptr, nullptr, src.data(), n, &m, &size, &bad);
+        CHECK(rc == TKV_OK && bad == n && m == want[t].size());
+        src.resize(m);
+        CHECK(src == want[t]);
+        uint64_t at = 0;
+        for (uint64_t j = 0; j < m && j < want[t].size(); ++j) {
+          CHECK(ikey_off[j] == at);
+          at += c.klen[want[t][j]] + 17;
+        }
+        CHECK(size == at);
+      }
+    });
+  for (auto& x : th) x.join();
+}
+
+// ---- tkv_sst_merge (4 runs, past 2^14 entries: the validation and the pairwise rounds on host threads) ----
+void check_sst_merge() {
+  std::vector<mg_ref::Case> cases;
+  std::vector<std::vector<uint64_t>> want;  // the surviving entries (run << 32 | index) in key order
+  // test_sst_merge_host.cpp's case above the threshold and three more of 18 000 to 21 000 entries, two of
+  // them with the drop-tombstones flag
+  for (const uint64_t seed : {1002, 1012, 1027, 1029}) {
+    cases.push_back(mg_ref::make_case(seed, 9000, 4));
+    want.push_back(mg_ref::insertion_merge(cases.back()));
+  }
+  std::vector<std::thread> th;
+  for (int t = 0; t < 4; ++t)
+    th.emplace_back([&, t] {
+      const mg_ref::Case& c = cases[t];
+      const mg_ref::Placed p(c);
+      uint64_t total = 0;
+      for (const uint64_t n : p.n) total += n;
+      CHECK(total >= (1u << 14));  // else the merge stays on the calling thread
+      for (int rep = 0; rep < 2; ++rep) {
+        std::vector<uint64_t> src(total, 0xA5A5A5A5A5A5A5A5ull);
+        uint64_t m = 0, kb = 0, vb = 0, bad = 0;
+        const int rc = tkv_sst_merge(4, p.pk.data(), p.size.data(), p.pko.data(), p.pkl.data(), p.pvo.data(), p.pvl.data(),
+                                     p.n.data(), p.base, p.bias.data(), c.flags, nullptr, nullptr, nullptr, nullptr,
+                                     src.data(), total, &m, &kb, &vb, &bad);
+        CHECK(rc == TKV_OK && bad == TKV_SST_MERGE_NONE && m == want[t].size());
+        src.resize(m);
+        CHECK(src == want[t]);
+      }
+    });
+  for (auto& x : th) x.join();
+}
+
 }  // namespace
 
 int main() {
@@ -359,6 +431,8 @@ int main() {
   check_multi_plans();
   check_wal_decode_host();
   check_wal_encode_layout();
+  check_memtable_build();
+  check_sst_merge();
   if (g_fail) {
     std::printf("%d FAILED\n", g_fail);
     return 1;

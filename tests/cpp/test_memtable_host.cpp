@@ -11,93 +11,12 @@
 #include <memory>
 #include <vector>
 
+#include "runs_reference.h"
 #include "tkv_crc32.h"
 
+using namespace mt_ref;  // the cases, compare and the insertion sort with replacement (replay)
+
 namespace {
-
-struct Rng {
-  std::uint64_t s;
-  std::uint64_t next() {
-    std::uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-  }
-  std::uint32_t below(std::uint32_t n) { return static_cast<std::uint32_t>(next() % n); }
-};
-
-// A heap block of exactly n elements (never a vector: its capacity may hide an overrun).
-template <class T>
-std::unique_ptr<T[]> exact(const std::vector<T>& v) {
-  std::unique_ptr<T[]> p(new T[v.size()]);
-  if (!v.empty()) std::memcpy(p.get(), v.data(), v.size() * sizeof(T));
-  return p;
-}
-
-struct Case {
-  std::vector<std::uint8_t> keys, op, tomb;
-  std::vector<std::uint64_t> koff, voff, seq;
-  std::vector<std::uint32_t> klen, vlen;
-  std::uint64_t ts;
-};
-
-Case make_case(std::uint64_t seed, std::uint32_t n_min, std::uint32_t n_max) {
-  Rng r{0x3E3E00 + seed};
-  Case c;
-  const std::uint32_t n = n_min + r.below(n_max - n_min + 1);
-  const std::uint8_t alpha_all[7] = {0x00, 0x01, 0x61, 0x62, 0x7F, 0x80, 0xFF};
-  const std::uint32_t na = 2 + r.below(6);
-  const bool views = seed % 5 == 0;
-  std::uint64_t vo = 0;
-  c.ts = r.next() >> 16;
-  if (views)
-    for (std::uint32_t k = 0; k < 64 + n / 4; ++k) c.keys.push_back(alpha_all[r.below(na)]);
-  for (std::uint32_t i = 0; i < n; ++i) {
-    const std::uint32_t kl = r.below(5) ? r.below(6) : r.below(41);
-    if (views) {
-      c.koff.push_back(r.below(static_cast<std::uint32_t>(c.keys.size()) - kl + 1));
-    } else {
-      c.koff.push_back(c.keys.size());
-      for (std::uint32_t k = 0; k < kl; ++k) c.keys.push_back(alpha_all[r.below(na)]);
-    }
-    c.klen.push_back(kl);
-    const std::uint32_t vl = r.below(9);
-    c.voff.push_back(vo);
-    c.vlen.push_back(vl);
-    vo += vl;
-    c.op.push_back(static_cast<std::uint8_t>(r.below(2)));
-    const std::uint8_t tb[6] = {0, 0, 1, 1, 2, 0xFF};
-    c.tomb.push_back(tb[r.below(6)]);
-    c.seq.push_back(r.next() >> 2);
-  }
-  return c;
-}
-
-// simd_comparator, one byte at a time.
-int compare(const Case& c, std::uint32_t x, std::uint32_t y) {
-  const std::uint32_t lx = c.klen[x], ly = c.klen[y];
-  for (std::uint32_t b = 0; b < lx && b < ly; ++b) {
-    const std::uint8_t p = c.keys[c.koff[x] + b], q = c.keys[c.koff[y] + b];
-    if (p != q) return p < q ? -1 : 1;
-  }
-  return lx < ly ? -1 : lx > ly ? 1 : 0;
-}
-
-// skiplist::insert record after record: the sorted list of record indices, an equal key replaced.
-std::vector<std::uint32_t> replay(const Case& c) {
-  std::vector<std::uint32_t> list;
-  for (std::uint32_t i = 0; i < c.klen.size(); ++i) {
-    std::size_t lo = 0, hi = list.size();  // the first node whose key is not smaller
-    while (lo < hi) {
-      const std::size_t mid = (lo + hi) / 2;
-      if (compare(c, list[mid], i) < 0) lo = mid + 1;
-      else hi = mid;
-    }
-    if (lo < list.size() && compare(c, list[lo], i) == 0) list[lo] = i;
-    else list.insert(list.begin() + static_cast<std::ptrdiff_t>(lo), i);
-  }
-  return list;
-}
 
 int failures = 0;
 #define CHECK(cond, ...)                     \

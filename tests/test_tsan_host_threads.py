@@ -1,6 +1,7 @@
 """ThreadSanitizer run of the host runtime's CPU-side threaded code (no GPU): the speculative
-parallel WAL chain walk with exact stitching and the multi-device split planner, each from several
-concurrent callers (tests/cpp/test_host_threads.cpp, Makefile target `tsan`)."""
+parallel WAL chain walk with exact stitching, the multi-device split planner, the host WAL decode and
+encode layout, and the memtable replay's threaded sort and the SSTable merge's threaded rounds, each from
+several concurrent callers (tests/cpp/test_host_threads.cpp, Makefile target `tsan`)."""
 import os
 import subprocess
 

@@ -241,7 +241,7 @@ THREADED_N = 50_000
 
 def host_threads():
     """How many threads the library's host loops use: the CPUs this process may run on, capped by
-    OMP_NUM_THREADS and 16 (tkv_formats.cpp host_threads, restated)."""
+    OMP_NUM_THREADS and 16 (tkv_host_util.h host_threads, restated)."""
     n = min(16, len(os.sched_getaffinity(0)))
     v = os.environ.get("OMP_NUM_THREADS", "")
     if v.strip().lstrip("+").isdigit() and int(v) > 0:

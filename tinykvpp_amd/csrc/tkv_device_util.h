@@ -1,6 +1,7 @@
 // Host-side launch and scratch plumbing shared by the .hip files: the HIP error return, grid
 // arithmetic, growing device arrays, the per-device scratch slot and its base (pinned result block,
-// device words, the wait for a tagged result) and the phase clock of the tkv_debug_*_phases hooks.
+// device words, the wait for a tagged result), the phase clock and the per-path stats of the
+// tkv_debug_*_last / tkv_debug_*_phases hooks, and the scratch take that reports TKV_OUT_OF_MEMORY.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -128,6 +129,42 @@ struct PhaseClock {
       if (x) (void)hipEventDestroy(x);
   }
 };
+
+// What a path's tkv_debug_*_last and tkv_debug_*_phases hooks report for the calling thread; each
+// path's .hip file keeps one thread_local instance. last[4]: what the thread's last device call did;
+// phase[4]: its phase times, device events at the phase boundaries while timing is set; taken: the
+// scratch bytes the call in progress has asked for (take below).
+struct PathStats {
+  std::uint64_t last[4] = {0, 0, 0, 0};
+  int timing = 0;
+  double phase[4] = {0, 0, 0, 0};
+  std::uint64_t taken = 0;
+  void begin() {  // a device call starts
+    for (auto& v : last) v = 0;
+    for (auto& v : phase) v = 0;
+    taken = 0;
+  }
+  void get_last(std::uint64_t out[4]) const {
+    for (int i = 0; i < 4; ++i) out[i] = last[i];
+  }
+  // Sets timing, copies the last call's phase times to out_ms (nullable); returns the earlier setting.
+  int phases(int enable, double* out_ms) {
+    const int prev = timing;
+    timing = enable ? 1 : 0;
+    if (out_ms)
+      for (int i = 0; i < 4; ++i) out_ms[i] = phase[i];
+    return prev;
+  }
+};
+
+// b.take for a path whose failed scratch allocation is the caller's TKV_OUT_OF_MEMORY with the path's
+// own text `msg`; the bytes asked for are added to `bytes`.
+template <class T>
+int take(DeviceBuf& b, std::uint64_t want, T** out, std::uint64_t& bytes, const char* msg) {
+  if (b.take(want, out) != TKV_OK) return set_error(TKV_OUT_OF_MEMORY, msg);
+  bytes += want * sizeof(T);
+  return TKV_OK;
+}
 
 // The calling thread's device's T, created on first use and kept for the process's lifetime. T's own
 // one-time initialisation stays with the caller, under T's own mutex.

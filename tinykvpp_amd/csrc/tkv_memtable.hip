@@ -441,24 +441,16 @@ struct MtScratch : ScratchBase {
   unsigned long long*& st = words;
 };
 
-// What the calling thread's last device build did (tkv_debug_memtable_last).
-thread_local std::uint64_t g_mt_last[4] = {0, 0, 0, 0};
+// The calling thread's device builds (tkv_debug_memtable_last, tkv_debug_memtable_phases).
+thread_local PathStats g_mt;
 // Which passes the calling thread's last device build launched (tkv_debug_memtable_passes): bit p of [0]
 // for a pass one workgroup ran, of [1] for one run as histogram, scan and scatter; [2] the passes run,
 // [3] the deepest histogram scan. Written by sort_list only.
 thread_local std::uint64_t g_mt_passes[4] = {0, 0, 0, 0};
-// Phase times of the calling thread's builds (tkv_debug_memtable_phases): device events at the phase
-// boundaries while g_mt_timing is set.
-thread_local int g_mt_timing = 0;
-thread_local double g_mt_phase[4] = {0, 0, 0, 0};
 
-// A failed allocation is the caller's TKV_OUT_OF_MEMORY.
-thread_local std::uint64_t g_taken = 0;  // scratch bytes the calling thread's build in progress asked for
 template <class T>
 int take(DeviceBuf& b, std::uint64_t want, T** out) {
-  if (b.take(want, out) != TKV_OK) return set_error(TKV_OUT_OF_MEMORY, "memtable build: scratch allocation failed");
-  g_taken += want * sizeof(T);
-  return TKV_OK;
+  return tkv::take(b, want, out, g_mt.taken, "memtable build: scratch allocation failed");
 }
 
 // In-place exclusive scan whose level 0 has been launched: the levels above it, then the bases back down.
@@ -497,7 +489,6 @@ int sort_list(const List* l, int cur, std::uint64_t m, std::uint64_t diffw, std:
 
 int build_locked(MtScratch& s, MtArgs a, const MemtableCall& c, hipStream_t st) {
   const std::uint64_t n = a.n;
-  g_taken = 0;
   List l[2];
   std::uint32_t* apos[2];
   for (int k = 0; k < 2; ++k) {
@@ -522,7 +513,7 @@ int build_locked(MtScratch& s, MtArgs a, const MemtableCall& c, hipStream_t st) 
   std::uint64_t tag = 0;
 
   // check and first word
-  PhaseClock clock(st, g_mt_timing != 0, g_mt_phase);
+  PhaseClock clock(st, g_mt.timing != 0, g_mt.phase);
   clock.mark(0);
   s.h_res[7] = 0;
   hipLaunchKernelGGL(mt_init, dim3(1), dim3(64), 0, st, s.st);
@@ -619,18 +610,17 @@ int build_locked(MtScratch& s, MtArgs a, const MemtableCall& c, hipStream_t st) 
   clock.mark(4);
   TKV_HIP_RC(hipStreamSynchronize(st));
   clock.finish();
-  g_mt_last[0] = a.m;
-  g_mt_last[1] = rounds;
-  g_mt_last[2] = second;
-  g_mt_last[3] = g_taken;
+  g_mt.last[0] = a.m;
+  g_mt.last[1] = rounds;
+  g_mt.last[2] = second;
+  g_mt.last[3] = g_mt.taken;
   return TKV_OK;
 }
 
 }  // namespace
 
 int memtable_build_device_impl(const MemtableCall& c, hipStream_t st) {
-  for (auto& v : g_mt_last) v = 0;
-  for (auto& v : g_mt_phase) v = 0;
+  g_mt.begin();
   for (auto& v : g_mt_passes) v = 0;
   MtScratch* sp = nullptr;
   if (int rc = per_device_scratch(&sp, kMtHres, kStWords, true)) return rc;
@@ -667,20 +657,12 @@ void tkv_debug_memtable_geom(uint64_t out[4]) {
   out[3] = tkv::kDecTile;
 }
 
-void tkv_debug_memtable_last(uint64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tkv::g_mt_last[i];
-}
+void tkv_debug_memtable_last(uint64_t out[4]) { tkv::g_mt.get_last(out); }
 
 void tkv_debug_memtable_passes(uint64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tkv::g_mt_passes[i];
 }
 
-int tkv_debug_memtable_phases(int enable, double out_ms[4]) {
-  const int prev = tkv::g_mt_timing;
-  tkv::g_mt_timing = enable ? 1 : 0;
-  if (out_ms)
-    for (int i = 0; i < 4; ++i) out_ms[i] = tkv::g_mt_phase[i];
-  return prev;
-}
+int tkv_debug_memtable_phases(int enable, double out_ms[4]) { return tkv::g_mt.phases(enable, out_ms); }
 
 }  // extern "C"

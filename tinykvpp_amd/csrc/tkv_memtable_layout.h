@@ -1,4 +1,4 @@
-// What the host path (tkv_formats.cpp) and the device kernels (tkv_memtable.hip) of the memtable replay
+// What the host path (tkv_runs_host.cpp) and the device kernels (tkv_memtable.hip) of the memtable replay
 // share (include/tkv_crc32.h "Memtable replay"): the metadata encode_internal_key puts behind a user key
 // (sstable_format.cpp:9-25), the comparison word of the sort and the limits.
 #pragma once

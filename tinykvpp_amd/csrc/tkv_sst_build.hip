@@ -398,15 +398,10 @@ struct SstScratch : ScratchBase {
   unsigned long long*& flags = words;
 };
 
-// What the calling thread's last device build did (tkv_debug_sst_build_last).
-thread_local std::uint64_t g_sst_last[4] = {0, 0, 0, 0};
-// Phase times of the calling thread's builds (tkv_debug_sst_build_phases): device events at the phase
-// boundaries while g_sst_timing is set.
-thread_local int g_sst_timing = 0;
-thread_local double g_sst_phase[4] = {0, 0, 0, 0};
+// The calling thread's device builds (tkv_debug_sst_build_last, tkv_debug_sst_build_phases).
+thread_local PathStats g_sst;
 
-int build_locked(SstScratch& s, SstArgs a, std::uint64_t cap, std::uint64_t block_cap, std::uint64_t* file_size,
-                 std::uint64_t* n_blocks, std::uint64_t* index_offset, std::uint64_t* index_size, hipStream_t st) {
+int build_locked(SstScratch& s, SstArgs a, const SstBuildCall& c, hipStream_t st) {
   const std::uint64_t n = a.n, n1 = a.n + 1u;
   const ScanPlan plan(n);
   if (int rc = s.S.take(n1, &a.S)) return rc;
@@ -422,7 +417,7 @@ int build_locked(SstScratch& s, SstArgs a, std::uint64_t cap, std::uint64_t bloc
   const dim3 gn1(blocks(n1, kScanThreads));
 
   // sizes
-  PhaseClock clock(st, g_sst_timing != 0, g_sst_phase);
+  PhaseClock clock(st, g_sst.timing != 0, g_sst.phase);
   clock.mark(0);
   TKV_HIP_RC(hipMemsetAsync(s.flags, 0, sizeof(unsigned long long), st));
   s.h_res[7] = 0;
@@ -475,12 +470,12 @@ int build_locked(SstScratch& s, SstArgs a, std::uint64_t cap, std::uint64_t bloc
   if (B == 0 || B > bmax) return set_error(TKV_IO_ERROR, "SSTable build: the cut is inconsistent");
   if (s.h_res[4] & kFlagBlock) return set_error(TKV_INVALID_ARGUMENT, "SSTable build: a data block does not fit u32");
   if (fsize > 0xFFFFFFFFull) return set_error(TKV_INVALID_ARGUMENT, "SSTable build: the file does not fit u32");
-  *file_size = fsize;
-  *n_blocks = B;
-  *index_offset = ioff;
-  *index_size = isz;
+  *c.file_size = fsize;
+  *c.n_blocks = B;
+  *c.index_offset = ioff;
+  *c.index_size = isz;
   const bool want_blocks = a.o_off || a.o_size || a.o_first;
-  if (fsize > cap || (want_blocks && B > block_cap))
+  if (fsize > c.cap || (want_blocks && B > c.block_cap))
     return set_error(TKV_BUFFER_OVERFLOW, "SSTable build: the file or the block arrays do not fit");
   if (!a.file) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
 
@@ -507,41 +502,35 @@ int build_locked(SstScratch& s, SstArgs a, std::uint64_t cap, std::uint64_t bloc
   clock.mark(4);
   TKV_HIP_RC(hipStreamSynchronize(st));
   clock.finish();
-  g_sst_last[0] = B;
-  g_sst_last[1] = rounds;
-  g_sst_last[2] = a.nwaves;
-  g_sst_last[3] = fsize;
+  g_sst.last[0] = B;
+  g_sst.last[1] = rounds;
+  g_sst.last[2] = a.nwaves;
+  g_sst.last[3] = fsize;
   return TKV_OK;
 }
 
 }  // namespace
 
-int sst_build_device_impl(const std::uint8_t* d_keys, const std::uint64_t* d_key_off, const std::uint32_t* d_key_len,
-                          const std::uint8_t* d_vals, const std::uint64_t* d_val_off, const std::uint32_t* d_val_len,
-                          std::uint64_t n, std::uint32_t target_block_size, std::uint8_t* d_file, std::uint64_t cap,
-                          std::uint64_t* d_block_off, std::uint32_t* d_block_size, std::uint32_t* d_block_first,
-                          std::uint64_t block_cap, std::uint64_t* file_size, std::uint64_t* n_blocks,
-                          std::uint64_t* index_offset, std::uint64_t* index_size, hipStream_t st) {
-  for (auto& v : g_sst_last) v = 0;
-  for (auto& v : g_sst_phase) v = 0;
+int sst_build_device_impl(const SstBuildCall& c, hipStream_t st) {
+  g_sst.begin();
   if (!device_tables(kAlgoCrc32)) return TKV_IO_ERROR;
   SstScratch* sp = nullptr;
   if (int rc = per_device_scratch(&sp, kSstHres, 1, false)) return rc;
   SstArgs a{};
-  a.keys = d_keys;
-  a.key_off = d_key_off;
-  a.key_len = d_key_len;
-  a.vals = d_vals;
-  a.val_off = d_val_off;
-  a.val_len = d_val_len;
-  a.n = n;
-  a.T = target_block_size;
-  a.file = d_file;
-  a.o_off = d_block_off;
-  a.o_size = d_block_size;
-  a.o_first = d_block_first;
+  a.keys = c.keys;
+  a.key_off = c.key_off;
+  a.key_len = c.key_len;
+  a.vals = c.vals;
+  a.val_off = c.val_off;
+  a.val_len = c.val_len;
+  a.n = c.n;
+  a.T = c.target_block_size;
+  a.file = c.file;
+  a.o_off = c.block_off;
+  a.o_size = c.block_size;
+  a.o_first = c.block_first;
   std::lock_guard<std::mutex> lk(sp->mu);
-  return build_locked(*sp, a, cap, block_cap, file_size, n_blocks, index_offset, index_size, st);
+  return build_locked(*sp, a, c, st);
 }
 
 }  // namespace tkv
@@ -555,16 +544,8 @@ void tkv_debug_sst_build_geometry(uint64_t out[4]) {
   out[3] = 0;
 }
 
-void tkv_debug_sst_build_last(uint64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tkv::g_sst_last[i];
-}
+void tkv_debug_sst_build_last(uint64_t out[4]) { tkv::g_sst.get_last(out); }
 
-int tkv_debug_sst_build_phases(int enable, double out_ms[4]) {
-  const int prev = tkv::g_sst_timing;
-  tkv::g_sst_timing = enable ? 1 : 0;
-  if (out_ms)
-    for (int i = 0; i < 4; ++i) out_ms[i] = tkv::g_sst_phase[i];
-  return prev;
-}
+int tkv_debug_sst_build_phases(int enable, double out_ms[4]) { return tkv::g_sst.phases(enable, out_ms); }
 
 }  // extern "C"

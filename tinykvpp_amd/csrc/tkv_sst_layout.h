@@ -1,7 +1,7 @@
 // The SSTable file image tkv_sst_build[_device] writes (include/tkv_crc32.h "SSTable flush"): the
 // arithmetic of sstable_writer::append / get_data_block / get_index / get_footer shared by the host
-// path (tkv_formats.cpp) and the device kernels (tkv_sst_build.hip), and the checks of the reader
-// tkv_sst_scan[_device] ("SSTable scan"; tkv_formats.cpp, tkv_sst_scan.hip). Plain C++.
+// path (tkv_sst_host.cpp) and the device kernels (tkv_sst_build.hip), and the checks of the reader
+// tkv_sst_scan[_device] ("SSTable scan"; tkv_sst_host.cpp, tkv_sst_scan.hip). Plain C++.
 #pragma once
 
 #include <cstdint>
@@ -69,7 +69,7 @@ inline std::uint32_t sst_rounds(std::uint64_t bmax) {
 }
 
 // ---- the reader's arithmetic (include/tkv_crc32.h "SSTable scan") -------------------
-// Shared by the host scan (tkv_formats.cpp) and the device kernels (tkv_sst_scan.hip). Nothing here
+// Shared by the host scan (tkv_sst_host.cpp) and the device kernels (tkv_sst_scan.hip). Nothing here
 // touches memory: a caller packs the (at most 5) bytes it may read into a word, bounded by what is left
 // of the region, and gets positions back; every sum is 64-bit.
 

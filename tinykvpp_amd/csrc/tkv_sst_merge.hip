@@ -392,24 +392,16 @@ struct MgScratch : ScratchBase {
   }
 };
 
-// What the calling thread's last device merge did (tkv_debug_sst_merge_last) and its phase times
-// (tkv_debug_sst_merge_phases).
-thread_local std::uint64_t g_mg_last[4] = {0, 0, 0, 0};
-thread_local int g_mg_timing = 0;
-thread_local double g_mg_phase[4] = {0, 0, 0, 0};
+// The calling thread's device merges (tkv_debug_sst_merge_last, tkv_debug_sst_merge_phases).
+thread_local PathStats g_mg;
 
-// A failed allocation is the caller's TKV_OUT_OF_MEMORY.
-thread_local std::uint64_t g_mg_taken = 0;
 template <class T>
 int take(DeviceBuf& b, std::uint64_t want, T** out) {
-  if (b.take(want, out) != TKV_OK) return set_error(TKV_OUT_OF_MEMORY, "sst merge: scratch allocation failed");
-  g_mg_taken += want * sizeof(T);
-  return TKV_OK;
+  return tkv::take(b, want, out, g_mg.taken, "sst merge: scratch allocation failed");
 }
 
 int merge_locked(MgScratch& s, const SstMergeCall& c, hipStream_t st) {
   const std::uint32_t K = c.n_runs;
-  g_mg_taken = 0;
   // the run table and the lists of the first round
   std::vector<MgRun> runs(K);
   std::vector<std::uint64_t> cut{0};
@@ -483,7 +475,7 @@ int merge_locked(MgScratch& s, const SstMergeCall& c, hipStream_t st) {
   const dim3 tb(kScanThreads);
 
   // check and sort entries
-  PhaseClock clock(st, g_mg_timing != 0, g_mg_phase);
+  PhaseClock clock(st, g_mg.timing != 0, g_mg.phase);
   clock.mark(0);
   s.h_res[7] = 0;
   hipLaunchKernelGGL(mg_init, dim3(1), dim3(64), 0, st, s.st);
@@ -537,18 +529,17 @@ int merge_locked(MgScratch& s, const SstMergeCall& c, hipStream_t st) {
   clock.mark(4);
   TKV_HIP_RC(hipStreamSynchronize(st));
   clock.finish();
-  g_mg_last[0] = n;
-  g_mg_last[1] = rounds;
-  g_mg_last[2] = rounds ? first[rounds] - first[rounds - 1u] : 0u;
-  g_mg_last[3] = g_mg_taken;
+  g_mg.last[0] = n;
+  g_mg.last[1] = rounds;
+  g_mg.last[2] = rounds ? first[rounds] - first[rounds - 1u] : 0u;
+  g_mg.last[3] = g_mg.taken;
   return TKV_OK;
 }
 
 }  // namespace
 
 int sst_merge_device_impl(const SstMergeCall& c, hipStream_t st) {
-  for (auto& v : g_mg_last) v = 0;
-  for (auto& v : g_mg_phase) v = 0;
+  g_mg.begin();
   MgScratch* sp = nullptr;
   if (int rc = per_device_scratch(&sp, kMgHres, kMsWords, true)) return rc;
   std::lock_guard<std::mutex> lk(sp->mu);
@@ -561,16 +552,8 @@ extern "C" {
 
 uint64_t tkv_debug_sst_merge_tile(void) { return tkv::kMgTile; }
 
-void tkv_debug_sst_merge_last(uint64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tkv::g_mg_last[i];
-}
+void tkv_debug_sst_merge_last(uint64_t out[4]) { tkv::g_mg.get_last(out); }
 
-int tkv_debug_sst_merge_phases(int enable, double out_ms[4]) {
-  const int prev = tkv::g_mg_timing;
-  tkv::g_mg_timing = enable ? 1 : 0;
-  if (out_ms)
-    for (int i = 0; i < 4; ++i) out_ms[i] = tkv::g_mg_phase[i];
-  return prev;
-}
+int tkv_debug_sst_merge_phases(int enable, double out_ms[4]) { return tkv::g_mg.phases(enable, out_ms); }
 
 }  // extern "C"

@@ -423,43 +423,25 @@ struct ScnScratch : ScratchBase {
   unsigned long long*& w = words;
 };
 
-thread_local int g_scn_timing = 0;
-thread_local double g_scn_phase[4] = {0, 0, 0, 0};
-thread_local std::uint64_t g_scn_last[4] = {0, 0, 0, 0};
+// The calling thread's device scans (tkv_debug_sst_scan_last, tkv_debug_sst_scan_phases).
+thread_local PathStats g_scn;
 
-// A failed allocation is the caller's TKV_OUT_OF_MEMORY.
 template <class T>
 int take(DeviceBuf& b, std::uint64_t want, T** out) {
-  if (b.take(want, out) != TKV_OK) return set_error(TKV_OUT_OF_MEMORY, "SSTable scan: scratch allocation failed");
-  return TKV_OK;
+  return tkv::take(b, want, out, g_scn.taken, "SSTable scan: scratch allocation failed");
 }
 
-struct ScanOut {
-  std::uint8_t* keys;
-  std::uint64_t keys_cap;
-  std::uint8_t* vals;
-  std::uint64_t vals_cap;
-  std::uint64_t entry_cap, block_cap;
-  std::uint64_t *n_entries, *n_blocks, *keys_size, *vals_size, *bad_block;
-};
-
-int corrupted(const ScanOut& o, std::uint64_t bad, const char* msg) {
-  *o.bad_block = bad;
-  *o.n_entries = *o.n_blocks = *o.keys_size = *o.vals_size = 0;
-  return set_error(TKV_CORRUPTED, msg);
-}
-
-int scan_locked(ScnScratch& s, ScanArgs a, const ScanOut& o, hipStream_t st) {
+int scan_locked(ScnScratch& s, ScanArgs a, const SstScanCall& o, hipStream_t st) {
   const dim3 tb(kScanThreads);
   a.w = s.w;
-  PhaseClock clock(st, g_scn_timing != 0, g_scn_phase);
+  PhaseClock clock(st, g_scn.timing != 0, g_scn.phase);
   clock.mark(0);
 
   // open
   s.h_res[7] = 0;
   hipLaunchKernelGGL(scn_open, dim3(1), dim3(64), 0, st, a, s.d_hres);
   if (int rc = s.wait(st, 7, 1, "SSTable scan: the open left no result")) return rc;
-  if (!s.h_res[3]) return corrupted(o, TKV_SST_BAD_FOOTER, "SSTable scan: the footer does not describe this file");
+  if (!s.h_res[3]) return sst_scan_corrupted(o, TKV_SST_BAD_FOOTER, "SSTable scan: the footer does not describe this file");
   a.ioff = s.h_res[0];
   a.isz = s.h_res[1];
   a.B = s.h_res[2];
@@ -533,9 +515,9 @@ int scan_locked(ScnScratch& s, ScanArgs a, const ScanOut& o, hipStream_t st) {
     hipLaunchKernelGGL(scn_publish, dim3(1), dim3(64), 0, st, a, none, none, none, s.d_hres);
   }
   if (int rc = s.wait(st, 7, 3, "SSTable scan: the parse left no result")) return rc;
-  if (s.h_res[0] & kBadFooterCrc) return corrupted(o, TKV_SST_BAD_FOOTER, "SSTable scan: corrupted index or footer");
-  if (!index_ok) return corrupted(o, TKV_SST_BAD_INDEX, "SSTable scan: the index framing does not hold");
-  if (s.h_res[1] < B) return corrupted(o, s.h_res[1], "SSTable scan: corrupted data block");
+  if (s.h_res[0] & kBadFooterCrc) return sst_scan_corrupted(o, TKV_SST_BAD_FOOTER, "SSTable scan: corrupted index or footer");
+  if (!index_ok) return sst_scan_corrupted(o, TKV_SST_BAD_INDEX, "SSTable scan: the index framing does not hold");
+  if (s.h_res[1] < B) return sst_scan_corrupted(o, s.h_res[1], "SSTable scan: corrupted data block");
   const std::uint64_t n = s.h_res[2];
   a.n = n;
   a.ktotal = s.h_res[3];
@@ -608,41 +590,34 @@ int scan_locked(ScnScratch& s, ScanArgs a, const ScanOut& o, hipStream_t st) {
   clock.mark(4);
   TKV_HIP_RC(hipStreamSynchronize(st));
   clock.finish();
-  g_scn_last[0] = B;
-  g_scn_last[1] = rounds;
-  g_scn_last[2] = a.nwaves;
-  g_scn_last[3] = static_cast<std::uint64_t>(kw) + vw;
+  g_scn.last[0] = B;
+  g_scn.last[1] = rounds;
+  g_scn.last[2] = a.nwaves;
+  g_scn.last[3] = static_cast<std::uint64_t>(kw) + vw;
   return TKV_OK;
 }
 
 }  // namespace
 
-int sst_scan_device_impl(const std::uint8_t* d_file, std::uint64_t file_size, std::uint32_t flags, std::uint64_t* d_key_off,
-                         std::uint32_t* d_key_len, std::uint64_t* d_val_off, std::uint32_t* d_val_len, std::uint64_t entry_cap,
-                         std::uint8_t* d_keys, std::uint64_t keys_cap, std::uint8_t* d_vals, std::uint64_t vals_cap,
-                         std::uint64_t* d_block_off, std::uint32_t* d_block_size, std::uint32_t* d_block_first,
-                         std::uint64_t block_cap, std::uint64_t* n_entries, std::uint64_t* n_blocks, std::uint64_t* keys_size,
-                         std::uint64_t* vals_size, std::uint64_t* bad_block, hipStream_t st) {
-  for (auto& v : g_scn_last) v = 0;
-  for (auto& v : g_scn_phase) v = 0;
+int sst_scan_device_impl(const SstScanCall& c, hipStream_t st) {
+  g_scn.begin();
   if (!device_tables(kAlgoCrc32)) return TKV_IO_ERROR;
   ScnScratch* sp = nullptr;
   if (int rc = per_device_scratch(&sp, kScnHres, 8, true)) return rc;
   ScanArgs a{};
-  a.file = d_file;
-  a.size = file_size;
-  a.key_views = (flags & TKV_SST_SCAN_KEY_VIEWS) ? 1u : 0u;
-  a.val_views = (flags & TKV_SST_SCAN_VAL_VIEWS) ? 1u : 0u;
-  a.o_key_off = d_key_off;
-  a.o_key_len = d_key_len;
-  a.o_val_off = d_val_off;
-  a.o_val_len = d_val_len;
-  a.o_block_off = d_block_off;
-  a.o_block_size = d_block_size;
-  a.o_block_first = d_block_first;
-  const ScanOut o{d_keys, keys_cap, d_vals, vals_cap, entry_cap, block_cap, n_entries, n_blocks, keys_size, vals_size, bad_block};
+  a.file = c.file;
+  a.size = c.file_size;
+  a.key_views = (c.flags & TKV_SST_SCAN_KEY_VIEWS) ? 1u : 0u;
+  a.val_views = (c.flags & TKV_SST_SCAN_VAL_VIEWS) ? 1u : 0u;
+  a.o_key_off = c.key_off;
+  a.o_key_len = c.key_len;
+  a.o_val_off = c.val_off;
+  a.o_val_len = c.val_len;
+  a.o_block_off = c.block_off;
+  a.o_block_size = c.block_size;
+  a.o_block_first = c.block_first;
   std::lock_guard<std::mutex> lk(sp->mu);
-  return scan_locked(*sp, a, o, st);
+  return scan_locked(*sp, a, c, st);
 }
 
 }  // namespace tkv
@@ -656,16 +631,8 @@ void tkv_debug_sst_scan_geometry(uint64_t out[4]) {
   out[3] = tkv::kScanBlock;
 }
 
-void tkv_debug_sst_scan_last(uint64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tkv::g_scn_last[i];
-}
+void tkv_debug_sst_scan_last(uint64_t out[4]) { tkv::g_scn.get_last(out); }
 
-int tkv_debug_sst_scan_phases(int enable, double out_ms[4]) {
-  const int prev = tkv::g_scn_timing;
-  tkv::g_scn_timing = enable ? 1 : 0;
-  if (out_ms)
-    for (int i = 0; i < 4; ++i) out_ms[i] = tkv::g_scn_phase[i];
-  return prev;
-}
+int tkv_debug_sst_scan_phases(int enable, double out_ms[4]) { return tkv::g_scn.phases(enable, out_ms); }
 
 }  // extern "C"

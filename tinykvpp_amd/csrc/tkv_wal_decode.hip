@@ -32,7 +32,6 @@
 #include "tkv_scan.h"
 #include "tkv_wal_copy.h"
 #include "tkv_wal_emit.h"
-#include "tkv_wal_device.h"
 #include "tkv_wal_layout.h"
 
 namespace tkv {
@@ -238,11 +237,9 @@ std::uint32_t launch_emit(const DecScratch& s, const DecArgs& a, std::uint8_t* d
   return launch_span_emit(s.ncu, e, st);
 }
 
-int decode_locked(DecScratch& s, DecArgs a, std::uint8_t* d_keys, std::uint64_t keys_cap, std::uint8_t* d_vals,
-                  std::uint64_t vals_cap, std::uint64_t* keys_size, std::uint64_t* vals_size, std::uint64_t* first_bad,
-                  hipStream_t st) {
+int decode_locked(DecScratch& s, DecArgs a, const WalDecodeCall& c, hipStream_t st) {
   if (a.size < kWalMeta) {  // no record fits (wal.cpp:68); the header pass relies on an image of 26 bytes
-    *first_bad = 0;
+    *c.first_bad = 0;
     return set_error(TKV_CORRUPTED, "WAL decode: a record fails wal_entry::decode's structural checks");
   }
   const ScanPlan plan(a.n);
@@ -263,17 +260,17 @@ int decode_locked(DecScratch& s, DecArgs a, std::uint8_t* d_keys, std::uint64_t 
   hipLaunchKernelGGL(dec_publish, dim3(1), dim3(64), 0, st, klv[levels], vlv[levels], s.first_bad, s.d_hres);
   if (int rc = s.wait(st, 3, 1, "WAL decode: the header pass left no result")) return rc;
   if (s.h_res[2] < a.n) {
-    *first_bad = s.h_res[2];
+    *c.first_bad = s.h_res[2];
     return set_error(TKV_CORRUPTED, "WAL decode: a record fails wal_entry::decode's structural checks");
   }
   a.ktotal = s.h_res[0];
   a.vtotal = s.h_res[1];
-  *keys_size = a.ktotal;
-  *vals_size = a.vtotal;
+  *c.keys_size = a.ktotal;
+  *c.vals_size = a.vtotal;
   const bool kcopy = !a.key_views && a.ktotal != 0, vcopy = !a.val_views && a.vtotal != 0;
-  if ((kcopy && a.ktotal > keys_cap) || (vcopy && a.vtotal > vals_cap))
+  if ((kcopy && a.ktotal > c.keys_cap) || (vcopy && a.vtotal > c.vals_cap))
     return set_error(TKV_BUFFER_OVERFLOW, "WAL decode: an arena does not fit its cap");
-  if ((kcopy && !d_keys) || (vcopy && !d_vals)) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
+  if ((kcopy && !c.keys) || (vcopy && !c.vals)) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
   a.ktile = static_cast<std::uint32_t*>(s.ktile.p);  // (an arena left as views keeps an earlier call's table: not read)
   a.vtile = static_cast<std::uint32_t*>(s.vtile.p);
   if (kcopy)
@@ -286,8 +283,8 @@ int decode_locked(DecScratch& s, DecArgs a, std::uint8_t* d_keys, std::uint64_t 
                      levels > 1 ? klv[1] : static_cast<const std::uint64_t*>(nullptr),
                      levels > 1 ? vlv[1] : static_cast<const std::uint64_t*>(nullptr));
   std::uint32_t kw = 0, vw = 0;
-  if (kcopy) kw = launch_emit<false>(s, a, d_keys, a.ktotal, st);
-  if (vcopy) vw = launch_emit<true>(s, a, d_vals, a.vtotal, st);
+  if (kcopy) kw = launch_emit<false>(s, a, c.keys, a.ktotal, st);
+  if (vcopy) vw = launch_emit<true>(s, a, c.vals, a.vtotal, st);
   TKV_HIP_RC(hipGetLastError());
   TKV_HIP_RC(hipStreamSynchronize(st));
   g_dec_last[0] = kw;
@@ -299,32 +296,27 @@ int decode_locked(DecScratch& s, DecArgs a, std::uint8_t* d_keys, std::uint64_t 
 
 }  // namespace
 
-int wal_decode_device_impl(const std::uint8_t* d_img, std::uint64_t size, const std::uint64_t* d_rec_off64,
-                           const std::uint32_t* d_rec_off32, std::uint64_t n, std::uint32_t flags, std::uint8_t* d_op,
-                           std::uint8_t* d_tomb, std::uint64_t* d_seq, std::uint64_t* d_key_off, std::uint32_t* d_key_len,
-                           std::uint64_t* d_val_off, std::uint32_t* d_val_len, std::uint8_t* d_keys, std::uint64_t keys_cap,
-                           std::uint8_t* d_vals, std::uint64_t vals_cap, std::uint64_t* keys_size, std::uint64_t* vals_size,
-                           std::uint64_t* first_bad, hipStream_t st) {
+int wal_decode_device_impl(const WalDecodeCall& c, hipStream_t st) {
   for (auto& v : g_dec_last) v = 0;
   DecScratch* sp = nullptr;
   if (int rc = per_device_scratch(&sp, kDecHres, 1, true)) return rc;
   DecArgs a{};
-  a.img = d_img;
-  a.size = size;
-  a.off64 = d_rec_off64;
-  a.off32 = d_rec_off32;
-  a.n = n;
-  a.key_views = (flags & TKV_WAL_DECODE_KEY_VIEWS) ? 1u : 0u;
-  a.val_views = (flags & TKV_WAL_DECODE_VAL_VIEWS) ? 1u : 0u;
-  a.op = d_op;
-  a.tomb = d_tomb;
-  a.seq = d_seq;
-  a.key_off = d_key_off;
-  a.key_len = d_key_len;
-  a.val_off = d_val_off;
-  a.val_len = d_val_len;
+  a.img = c.img;
+  a.size = c.size;
+  a.off64 = c.rec_off64;
+  a.off32 = c.rec_off32;
+  a.n = c.n;
+  a.key_views = (c.flags & TKV_WAL_DECODE_KEY_VIEWS) ? 1u : 0u;
+  a.val_views = (c.flags & TKV_WAL_DECODE_VAL_VIEWS) ? 1u : 0u;
+  a.op = c.op;
+  a.tomb = c.tomb;
+  a.seq = c.seq;
+  a.key_off = c.key_off;
+  a.key_len = c.key_len;
+  a.val_off = c.val_off;
+  a.val_len = c.val_len;
   std::lock_guard<std::mutex> lk(sp->mu);
-  return decode_locked(*sp, a, d_keys, keys_cap, d_vals, vals_cap, keys_size, vals_size, first_bad, st);
+  return decode_locked(*sp, a, c, st);
 }
 
 }  // namespace tkv

@@ -1,5 +1,5 @@
 // Device-side WAL recovery verify (tkv_wal_device.hip), used by tkv_wal_verify and
-// tkv_wal_verify_device (tkv_formats.cpp).
+// tkv_wal_verify_device (tkv_wal_host.cpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -56,28 +56,5 @@ int wal_salvage_add_base(std::uint64_t* d_off64, std::uint64_t n, std::uint64_t 
 // The calling thread's six salvage counters (tkv_debug_wal_salvage_last): resynchronisations, search
 // spans, start offsets tested, candidates folded, their payload bytes, index calls.
 std::uint64_t* wal_salvage_last();
-
-// WAL group-commit encode on `st` (tkv_wal_encode.hip; synchronous): the size scan, the host's
-// overflow / invalid decision from its pinned result, then the emit into [d_img, d_img + total) with the
-// CRC of every record of record_len <= 240 folded in the same pass and the longer ones stamped by one
-// CRC batch over the written image. Arguments and results are tkv_wal_encode_device's (n >= 1 and the
-// required pointers checked by the caller).
-int wal_encode_device_impl(const std::uint8_t* d_keys, const std::uint64_t* d_key_off, const std::uint32_t* d_key_len,
-                           const std::uint8_t* d_vals, const std::uint64_t* d_val_off, const std::uint32_t* d_val_len,
-                           const std::uint8_t* d_op, const std::uint8_t* d_tomb, const std::uint64_t* d_seq,
-                           std::uint64_t first_seq, std::uint64_t n, std::uint8_t* d_img, std::uint64_t cap,
-                           std::uint64_t* d_rec_off, std::uint32_t* d_crc, std::uint64_t* img_size, hipStream_t st);
-
-// Batched WAL decode on `st` (tkv_wal_decode.hip; synchronous): the header pass as level 0 of the key
-// and value length scans, the host's corrupted / overflow decision from its pinned result, then the
-// columns, the arena offsets and the emit of every copied arena. Arguments and results are
-// tkv_wal_decode_device's (n >= 1, the flags, the offset arrays and the required pointers checked by
-// the caller, who also presets *keys_size = *vals_size = 0).
-int wal_decode_device_impl(const std::uint8_t* d_img, std::uint64_t size, const std::uint64_t* d_rec_off64,
-                           const std::uint32_t* d_rec_off32, std::uint64_t n, std::uint32_t flags, std::uint8_t* d_op,
-                           std::uint8_t* d_tomb, std::uint64_t* d_seq, std::uint64_t* d_key_off, std::uint32_t* d_key_len,
-                           std::uint64_t* d_val_off, std::uint32_t* d_val_len, std::uint8_t* d_keys, std::uint64_t keys_cap,
-                           std::uint8_t* d_vals, std::uint64_t vals_cap, std::uint64_t* keys_size, std::uint64_t* vals_size,
-                           std::uint64_t* first_bad, hipStream_t st);
 
 }  // namespace tkv

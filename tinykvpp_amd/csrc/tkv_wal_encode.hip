@@ -37,7 +37,6 @@
 #include "tkv_engine.h"
 #include "tkv_scan.h"
 #include "tkv_wal_copy.h"
-#include "tkv_wal_device.h"
 #include "tkv_wal_fold.h"
 #include "tkv_wal_layout.h"
 
@@ -303,7 +302,7 @@ std::atomic<int> g_enc_fused{1};
 // What the calling thread's last device encode did (tkv_debug_wal_encode_last).
 thread_local std::uint64_t g_enc_last[4] = {0, 0, 0, 0};
 
-int encode_locked(EncScratch& s, EncArgs a, std::uint64_t cap, std::uint64_t* img_size, hipStream_t st) {
+int encode_locked(EncScratch& s, EncArgs a, const WalEncodeCall& c, hipStream_t st) {
   const ScanPlan plan(a.n);
   const int levels = plan.levels;
   std::uint64_t* sums = nullptr;
@@ -320,8 +319,8 @@ int encode_locked(EncScratch& s, EncArgs a, std::uint64_t cap, std::uint64_t* im
   if (int rc = s.wait(st, 3, 1, "WAL encode: the size scan left no result")) return rc;
   const std::uint64_t total = s.h_res[0], nlong = s.h_res[2];
   if (s.h_res[1]) return set_error(TKV_INVALID_ARGUMENT, "WAL encode: 18 + key_len + val_len does not fit u32");
-  *img_size = total;
-  if (total > cap) return set_error(TKV_BUFFER_OVERFLOW, "WAL encode: the image does not fit cap");
+  *c.img_size = total;
+  if (total > c.cap) return set_error(TKV_BUFFER_OVERFLOW, "WAL encode: the image does not fit cap");
   if (!a.img) return set_error(TKV_INVALID_ARGUMENT, "null pointer");
   a.total = total;
   a.ntiles = (total + kEncTile - 1u) / kEncTile;
@@ -355,35 +354,31 @@ int encode_locked(EncScratch& s, EncArgs a, std::uint64_t cap, std::uint64_t* im
 
 }  // namespace
 
-int wal_encode_device_impl(const std::uint8_t* d_keys, const std::uint64_t* d_key_off, const std::uint32_t* d_key_len,
-                           const std::uint8_t* d_vals, const std::uint64_t* d_val_off, const std::uint32_t* d_val_len,
-                           const std::uint8_t* d_op, const std::uint8_t* d_tomb, const std::uint64_t* d_seq,
-                           std::uint64_t first_seq, std::uint64_t n, std::uint8_t* d_img, std::uint64_t cap,
-                           std::uint64_t* d_rec_off, std::uint32_t* d_crc, std::uint64_t* img_size, hipStream_t st) {
+int wal_encode_device_impl(const WalEncodeCall& c, hipStream_t st) {
   for (auto& v : g_enc_last) v = 0;
   const DeviceTables* tabs = device_tables(kAlgoCrc32);
   if (!tabs) return TKV_IO_ERROR;
   EncScratch* sp = nullptr;
   if (int rc = per_device_scratch(&sp, kEncHres, kCntWords, false)) return rc;
   EncArgs a{};
-  a.keys = d_keys;
-  a.key_off = d_key_off;
-  a.key_len = d_key_len;
-  a.vals = d_vals;
-  a.val_off = d_val_off;
-  a.val_len = d_val_len;
-  a.op = d_op;
-  a.tomb = d_tomb;
-  a.seq = d_seq;
-  a.first_seq = first_seq;
-  a.n = n;
-  a.img = d_img;
-  a.rec_off = d_rec_off;
-  a.crc = d_crc;
+  a.keys = c.keys;
+  a.key_off = c.key_off;
+  a.key_len = c.key_len;
+  a.vals = c.vals;
+  a.val_off = c.val_off;
+  a.val_len = c.val_len;
+  a.op = c.op;
+  a.tomb = c.tomb;
+  a.seq = c.seq;
+  a.first_seq = c.first_seq;
+  a.n = c.n;
+  a.img = c.img;
+  a.rec_off = c.rec_off;
+  a.crc = c.crc;
   a.fused = g_enc_fused.load() ? 1u : 0u;
   a.tabs = tabs;
   std::lock_guard<std::mutex> lk(sp->mu);
-  return encode_locked(*sp, a, cap, img_size, st);
+  return encode_locked(*sp, a, c, st);
 }
 
 }  // namespace tkv

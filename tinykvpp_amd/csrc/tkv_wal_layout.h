@@ -1,7 +1,7 @@
 // The WAL record wal_entry::encode writes (wal.cpp:19-61), little-endian and packed:
 //   u32 record_len | u32 crc32 | u8 op | u64 seq | u8 tombstone | u32 key_len | u32 val_len | key | value
 // record_len counts the bytes behind the 8-byte prefix, and crc32 covers exactly those. Plain C++:
-// shared by the host walk (tkv_formats.cpp) and the device kernels (tkv_wal_*.hip).
+// shared by the host walk (tkv_wal_host.cpp) and the device kernels (tkv_wal_*.hip).
 #pragma once
 
 #include <cstdint>

@@ -15,8 +15,9 @@ fi
 H=$T/tinykvpp_amd/csrc
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -I$T/include -I$H"
 mkdir -p abl
-for f in $H/*.hip; do s=$(basename $f); /opt/rocm/bin/hipcc $F "$@" -c $H/$s -o $T/${s%.*}.o & done
-for s in tkv_crc32_host.cpp tkv_formats.cpp tkv_crc32_span.cpp; do /opt/rocm/bin/hipcc $F "$@" -x hip -c $H/$s -o $T/${s%.*}.o & done
+# every source of the revision's csrc (its build/ is not there: not archived, removed above)
+for f in $H/*.hip; do s=$(basename $f); /opt/rocm/bin/hipcc $F "$@" -c $f -o $T/${s%.*}.o & done
+for f in $H/*.cpp; do s=$(basename $f); /opt/rocm/bin/hipcc $F "$@" -x hip -c $f -o $T/${s%.*}.o & done
 wait
 echo "extern \"C\" const char* tkv_build_id(void) { return \"rev-$REV\"; }" > $T/id.cpp
 /opt/rocm/bin/hipcc -O2 -fPIC -c -x c++ $T/id.cpp -o $T/id.o
