@@ -103,9 +103,11 @@ def build_device(batch=None, timestamp_ms=0, stream=None, **columns):
     kinds = {"u8": torch.uint8, "u64": torch.int64, "u32": torch.int32}
 
     def alloc(count, kind):
-        # (an arena without a byte still gets an address: sst.build_device requires one)
-        t = torch.empty(max(count, 1), dtype=kinds[kind], device=dev)[:count] if kind == "u8" else \
-            torch.empty(count, dtype=kinds[kind], device=dev)
+        # (an arena without a byte has no address: data_ptr() of an empty tensor is 0. So MemtableRun.vals
+        # may be such a tensor, when the batch has no value arena or an empty one. sst.build_device stands a
+        # spare byte in for it and sst.merge_device leaves it out; any other caller that hands run.vals to
+        # a C call beside a non-NULL val_len has to do the same, or the call answers "null pointer")
+        t = torch.empty(count, dtype=kinds[kind], device=dev)
         if other:
             t.record_stream(stream)
         return t

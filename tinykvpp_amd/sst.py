@@ -198,6 +198,17 @@ def build_device(keys, key_off, key_len, vals=None, val_off=None, val_len=None, 
 
     def ptr(t):
         return None if t is None else ctypes.c_void_p(t.data_ptr())
+    # An arena without a byte has no address (data_ptr() of an empty tensor is 0), and the call requires one
+    # for keys, and for vals beside val_len: a batch whose values are all empty, decoded into a copied arena
+    # and replayed, arrives here like that. A spare byte stands in (uninitialised, alive until this function
+    # returns, which is after the stream's end): every sound span into an arena without a byte is empty, so the
+    # byte is never read. The call takes no arena sizes, so a key_len or val_len above 0 beside an empty arena
+    # is the caller's error here as it is beside any arena that is too short; it used to be refused as a null
+    # pointer and would now read that byte.
+    if keys.numel() == 0:
+        keys = alloc(1, torch.uint8)
+    if val_len is not None and vals.numel() == 0:
+        vals = alloc(1, torch.uint8)
     lib = load_library()
     st = _launch_stream(stream, dev)
     sizes = [ctypes.c_uint64(0) for _ in range(4)]  # file_size, n_blocks, index_offset, index_size
