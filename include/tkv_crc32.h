@@ -740,6 +740,15 @@ size_t tkv_debug_wal_rounds(uint64_t *out, size_t n);
 /* Fix-up rounds a device WAL verify or index may take before it hands the image to the exact host walk
  * (default 256; 0 restores it). Returns the previous value. Tests set 1 to reach the hand-over. */
 uint64_t tkv_debug_set_wal_round_budget(uint64_t rounds);
+/* A cap on the waves of the device WAL sweep: a verify, index, salvage or recovery of nreg regions runs
+ * min(nreg, 12 waves per compute unit, waves) of them, each over a contiguous chunk of regions (0: no
+ * cap, the default). Process-wide, read once per sweep. Returns the previous value. Tests set 1-5 so
+ * that images of a few regions run chunks of several regions, as images of tens of MB do. */
+uint32_t tkv_debug_set_wal_sweep_waves(uint32_t waves);
+/* Geometry of the device WAL sweep: out[0] = image bytes per region, out[1] = bytes per lane piece of
+ * a region, out[2] = the waves of the calling thread's last sweep, out[3] = its regions (both 0 before
+ * the first). */
+void tkv_debug_wal_sweep_geometry(uint64_t out[4]);
 /* Which path the last irregular batch on `stream` took: 1 = byte-stream row walk (blocks back to
  * back, each at least 64 bytes), 0 = general row walk; -1 on error. Synchronizes
  * the stream. */

@@ -133,6 +133,8 @@ SIGNATURES = {
     "tkv_debug_wal_last": (None, [_vp]),
     "tkv_debug_wal_rounds": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
     "tkv_debug_set_wal_round_budget": (_u64, [_u64]),
+    "tkv_debug_set_wal_sweep_waves": (ctypes.c_uint32, [ctypes.c_uint32]),
+    "tkv_debug_wal_sweep_geometry": (None, [_vp]),
     "tkv_debug_update_counts": (None, [_vp]),
     "tkv_debug_update_counts_n": (_sz, [_vp, _sz]),
     "tkv_debug_irregular_mode": (_int, [_vp]),
@@ -146,6 +148,7 @@ SIGNATURES = {
 
 # symbols an older build may lack (tools/ab_lib.py loads earlier builds for A/B runs)
 OPTIONAL = {"tkv_build_id", "tkv_wal_index_device", "tkv_wal_index", "tkv_debug_set_wal_round_budget",
+            "tkv_debug_set_wal_sweep_waves", "tkv_debug_wal_sweep_geometry",
             "tkv_debug_set_packed_fold", "tkv_wal_encode_device", "tkv_wal_encode", "tkv_debug_wal_encode_layout",
             "tkv_debug_wal_encode_geometry", "tkv_debug_wal_encode_last", "tkv_debug_set_wal_encode_fused",
             "tkv_wal_decode_device", "tkv_wal_decode_host", "tkv_debug_wal_decode_geometry",

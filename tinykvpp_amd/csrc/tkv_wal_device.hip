@@ -1270,6 +1270,9 @@ struct WalScratch {
 constexpr std::uint64_t kRoundBudget = 256;
 // the budget in force (tkv_debug_set_wal_round_budget: tests reach the host-walk hand-over with a small one)
 std::atomic<std::uint64_t> g_round_budget{kRoundBudget};
+// a cap on the sweep's waves (tkv_debug_set_wal_sweep_waves; 0: none): tests run small images through
+// chunks of several regions, which only images of tens of MB reach otherwise
+std::atomic<std::uint32_t> g_sweep_waves{0};
 
 // What the calling thread's last WAL verify did (tkv_debug_wal_last).
 thread_local std::uint64_t g_last[4] = {0, 0, 0, 0};  // rounds, host walk needed, image copied, no fix-up
@@ -1277,6 +1280,8 @@ thread_local std::uint64_t g_last[4] = {0, 0, 0, 0};  // rounds, host walk neede
 // range and all tasks' ranges in regions, the most regions one task walked and all walked regions
 // (tkv_debug_wal_rounds)
 thread_local std::vector<std::uint64_t> g_rounds;
+// the waves and regions of the calling thread's last sweep (tkv_debug_wal_sweep_geometry)
+thread_local std::uint64_t g_sweep_last[2] = {0, 0};
 
 constexpr std::uint64_t kRawUnit = 8 + 4 * 4, kDenseUnit = 8 + 5 * 4;
 
@@ -1377,7 +1382,10 @@ int verify_locked(WalScratch& s, const std::uint8_t* w, std::uint64_t size, std:
   if (nreg64 >= 0xFFFFFFF0ull) return set_error(TKV_INVALID_ARGUMENT, "WAL image too large for the device walk");
   const std::uint32_t nreg = static_cast<std::uint32_t>(nreg64);
   if (int rc = grow(&s.regs, &s.cap_reg, nreg, 3 * 8 + 8 * 4)) return rc;
-  const std::uint32_t W = static_cast<std::uint32_t>(std::min<std::uint64_t>(nreg, s.cap_waves));
+  std::uint32_t W = static_cast<std::uint32_t>(std::min<std::uint64_t>(nreg, s.cap_waves));
+  if (const std::uint32_t cap = g_sweep_waves.load(std::memory_order_relaxed)) W = std::min(W, cap);
+  g_sweep_last[0] = W;
+  g_sweep_last[1] = nreg;
   // a wave's segment holds the long payloads of its chunk's chain (>= kLaneFold + 8 bytes apart);
   // more (speculative chains) and the fix-ups' go to the atomic area behind the segments
   const std::uint64_t seg = (static_cast<std::uint64_t>((nreg + W - 1) / W) * kRegion) / (kLaneFold + 8) + 16;
@@ -1768,6 +1776,15 @@ extern "C" void tkv_debug_wal_last(uint64_t out[4]) {
 
 extern "C" uint64_t tkv_debug_set_wal_round_budget(uint64_t rounds) {
   return tkv::g_round_budget.exchange(rounds ? rounds : tkv::kRoundBudget);
+}
+
+extern "C" uint32_t tkv_debug_set_wal_sweep_waves(uint32_t waves) { return tkv::g_sweep_waves.exchange(waves); }
+
+extern "C" void tkv_debug_wal_sweep_geometry(uint64_t out[4]) {
+  out[0] = tkv::kRegion;
+  out[1] = tkv::kPiece;
+  out[2] = tkv::g_sweep_last[0];
+  out[3] = tkv::g_sweep_last[1];
 }
 
 extern "C" size_t tkv_debug_wal_rounds(uint64_t* out, size_t n) {
