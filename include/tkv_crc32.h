@@ -794,6 +794,20 @@ int tkv_debug_set_one_pass(int enable);
  * always does (kept so one process can run both on the same buffers). Returns the previous setting.
  * Default 1. */
 int tkv_debug_set_packed_fold(int enable);
+/* Packed uniform batches of 4 KiB blocks. Each returns the previous setting; both are
+ * kept so one process can run old and new on the same buffers, and every setting gives the same CRCs.
+ * window: result registers (64 results each) a wave keeps before it stores any, 0..4 (other values are
+ * clamped); 0 stores each register as soon as it is full. Default 4.
+ * order: the waves take the batch's whole rounds of 16 x waves blocks in chunks of 16 consecutive blocks,
+ * wave w chunks w, w + waves, ..., and share the rest evenly, unless this is 0: then every wave takes one
+ * contiguous range of blocks. Default 1. */
+int tkv_debug_set_packed_window(int registers);
+int tkv_debug_set_packed_order(int enable);
+/* tkv_crc32_batch_uniform_device with every block starting from the raw register init_raw instead of
+ * 0xFFFFFFFF (the uniform kernels take any such register; the public entries only pass it for single
+ * spans, so this keeps it under test on batches). */
+int tkv_debug_batch_uniform_init_device(const uint8_t *d_base, uint64_t stride, uint64_t len, uint32_t init_raw,
+                                        uint32_t *d_out_final, uint64_t n, void *stream);
 /* The host layout step of tkv_wal_encode alone (no GPU): the records with their CRC fields zero, what
  * wal.cpp:27-52 leaves before line 54. Arguments as tkv_wal_encode; returns the number of records laid
  * out (0 on an argument error or when total > cap) and sets *img_size as tkv_wal_encode does. */

@@ -122,6 +122,9 @@ SIGNATURES = {
     "tkv_debug_set_stream_groups": (_int, [_int]),
     "tkv_debug_set_one_pass": (_int, [_int]),
     "tkv_debug_set_packed_fold": (_int, [_int]),
+    "tkv_debug_set_packed_window": (_int, [_int]),
+    "tkv_debug_set_packed_order": (_int, [_int]),
+    "tkv_debug_batch_uniform_init_device": (_int, [_u8p, _u64, _u64, _u32, _vp, _u64, _vp]),
     "tkv_debug_wal_encode_layout": (_sz, [_u8p, _vp, _vp, _u8p, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u8p, _u64,
                                           ctypes.POINTER(_u64)]),
     "tkv_debug_wal_encode_geometry": (None, [_vp]),
@@ -149,7 +152,8 @@ SIGNATURES = {
 # symbols an older build may lack (tools/ab_lib.py loads earlier builds for A/B runs)
 OPTIONAL = {"tkv_build_id", "tkv_wal_index_device", "tkv_wal_index", "tkv_debug_set_wal_round_budget",
             "tkv_debug_set_wal_sweep_waves", "tkv_debug_wal_sweep_geometry",
-            "tkv_debug_set_packed_fold", "tkv_wal_encode_device", "tkv_wal_encode", "tkv_debug_wal_encode_layout",
+            "tkv_debug_set_packed_fold", "tkv_debug_set_packed_window", "tkv_debug_set_packed_order",
+            "tkv_debug_batch_uniform_init_device", "tkv_wal_encode_device", "tkv_wal_encode", "tkv_debug_wal_encode_layout",
             "tkv_debug_wal_encode_geometry", "tkv_debug_wal_encode_last", "tkv_debug_set_wal_encode_fused",
             "tkv_wal_decode_device", "tkv_wal_decode_host", "tkv_debug_wal_decode_geometry",
             "tkv_debug_wal_decode_last", "tkv_wal_resync_device", "tkv_wal_salvage_device", "tkv_wal_salvage",

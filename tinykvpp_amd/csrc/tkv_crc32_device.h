@@ -1033,9 +1033,19 @@ __device__ __forceinline__ void crc_stream_body(const RowsArgs& a, std::uint32_t
 // blocks of more than one row; tkv_crc32_kernels.hip).
 // FOLD: each lane first shortens its 64 bytes to 40 with the sparse-multiple fold (fold_segment above;
 // CRC-32 tables only), so a row costs 48 slicing lookups instead of 72.
-template <int DEPTH, int ILP, bool R1, int SKEW = 0, int PRIO = 0, bool FOLD = false>
+// CHUNK (R1 only; 0: off, else a power of two): chunk-strided block order. The batch's whole rounds of
+// W * CHUNK blocks are dealt out in chunks of CHUNK consecutive blocks, wave w taking chunks w, w + W,
+// w + 2 W, ... so that all waves sweep one window of W * CHUNK blocks through memory instead of W
+// separate ranges; the blocks left after the last whole round are split evenly and contiguously, as the
+// whole batch is without CHUNK (a batch of fewer than W * CHUNK blocks is all remainder).
+// a.packed_win (R1 only, 0..4): result registers a wave keeps before it stores any (64 results each;
+// the store of a full window's oldest register is the only one inside the row loop). 0: every register
+// is stored as soon as it is full.
+template <int DEPTH, int ILP, bool R1, int SKEW = 0, int PRIO = 0, bool FOLD = false, int CHUNK = 0>
 __device__ __forceinline__ void crc_packed_body(const RowsArgs& a, std::uint32_t* lds) {
   static_assert(DEPTH > ILP && DEPTH % ILP == 0, "DEPTH must be a multiple of ILP and exceed it");
+  static_assert(R1 || CHUNK == 0, "chunk-strided block order: one-row blocks only");
+  static_assert((CHUNK & (CHUNK - 1)) == 0 && (CHUNK == 0 || SKEW == 0), "CHUNK: a power of two, even split");
   const std::uint32_t lane = threadIdx.x & 63u;
   const LaneConst kc = lane_const(lane);
   const std::uint32_t hcon = a.tabs->horner[lane & 31u];  // Shift_4096(1 << (l & 31))
@@ -1050,6 +1060,7 @@ __device__ __forceinline__ void crc_packed_body(const RowsArgs& a, std::uint32_t
   const std::uint64_t W = a.nwaves;
   const std::uint32_t R = R1 ? 1u : a.len / kRow;
   std::uint32_t b0, nb;
+  std::uint32_t nchunked = 0;  // CHUNK: blocks of this wave that come in chunks (the same for every wave)
   if constexpr (SKEW != 0) {
     constexpr std::uint32_t w0 = 256, w1 = SKEW, w2 = w1 * SKEW / 256, w3 = w2 * SKEW / 256;
     constexpr std::uint32_t tot = 4 * (w0 + w1 + w2 + w3);
@@ -1062,17 +1073,35 @@ __device__ __forceinline__ void crc_packed_body(const RowsArgs& a, std::uint32_t
     b0 = static_cast<std::uint32_t>(g0 + gn * pre / tot);
     nb = static_cast<std::uint32_t>(g0 + gn * (pre + wk) / tot) - b0;
   } else {
-    b0 = static_cast<std::uint32_t>(wave * static_cast<std::uint64_t>(a.nblocks) / W);
-    nb = static_cast<std::uint32_t>((wave + 1) * static_cast<std::uint64_t>(a.nblocks) / W) - b0;
+    // whole rounds of W * CHUNK blocks go out in chunks (none without CHUNK); the rest is split evenly
+    std::uint32_t done = 0;
+    if constexpr (CHUNK != 0) {
+      const std::uint32_t per_round = static_cast<std::uint32_t>(W) * CHUNK;
+      nchunked = a.nblocks / per_round * CHUNK;
+      done = a.nblocks / per_round * per_round;
+    }
+    const std::uint64_t rest = a.nblocks - done;
+    b0 = done + static_cast<std::uint32_t>(wave * rest / W);
+    nb = nchunked + done + static_cast<std::uint32_t>((wave + 1) * rest / W) - b0;
   }
-  const std::uint32_t nrows = nb * R;  // wave-local rows j = 0 .. nrows-1, contiguous in memory
+  // Batch index of the wave's k-th block: chunk k / CHUNK of the wave, then its even share of the rest
+  // from b0 on. Wave-uniform k: scalar arithmetic.
+  auto block_of = [&](auto k) {
+    if constexpr (CHUNK != 0) {
+      const auto chunked = ((k / CHUNK) * static_cast<std::uint32_t>(W) + wave) * CHUNK + (k & (CHUNK - 1u));
+      return k < nchunked ? chunked : b0 + (k - nchunked);
+    } else {
+      return b0 + k;
+    }
+  };
+  const std::uint32_t nrows = nb * R;  // wave-local rows j = 0 .. nrows-1 (without CHUNK: contiguous in memory)
   const std::uintptr_t lane_base =
-      reinterpret_cast<std::uintptr_t>(a.base) + static_cast<std::uint64_t>(b0) * R * kRow + lane * kSeg;
+      reinterpret_cast<std::uintptr_t>(a.base) + (CHUNK ? 0ull : static_cast<std::uint64_t>(b0) * R * kRow) + lane * kSeg;
 
   uint4 buf[DEPTH][4];
   auto issue = [&](std::uint32_t j, uint4 (&q)[4]) {
     const std::uint32_t jc = j < nrows ? j : nrows - 1;  // rows past the range reload the last one
-    const std::uintptr_t p = lane_base + static_cast<std::uint64_t>(jc) * kRow;
+    const std::uintptr_t p = lane_base + static_cast<std::uint64_t>(CHUNK ? block_of(jc) : jc) * kRow;
 #pragma unroll
     for (int i = 0; i < 4; ++i) q[i] = gload16(p + 16u * i);
   };
@@ -1081,13 +1110,20 @@ __device__ __forceinline__ void crc_packed_body(const RowsArgs& a, std::uint32_t
   std::uint32_t r = 0;     // row within the current block
   std::uint32_t k = 0;     // wave-local index of the current block
   std::uint32_t keep = 0;  // lane i: result of wave-local block (k & ~63) + i
+  // Full registers kept back (R1, a.packed_win > 1): held1 the newest, 64 blocks before keep's
+  // (explicit slots: a runtime index would put them in scratch memory).
+  std::uint32_t held1 = 0, held2 = 0, held3 = 0, nheld = 0;
+  const std::uint32_t win = R1 ? a.packed_win : 0u;
+  auto store64 = [&](std::uint32_t first, std::uint32_t upto, std::uint32_t val) {  // blocks first .. first + upto
+    if (lane <= upto) a.out[block_of(first + lane)] = val;
+  };
   auto finish = [&](std::uint32_t v) {
     std::uint32_t term;
     const bool head = R1 || r == 0;
     if (head) {
       term = inj_const;
       if (a.init_raw) {
-        const std::uint32_t init = sload32(a.init_raw, b0 + k);
+        const std::uint32_t init = sload32(a.init_raw, block_of(k));
         term = lo_half ? 0u : static_cast<std::uint32_t>(__builtin_amdgcn_sbfe(static_cast<std::int32_t>(init),
                                                                                 lane & 31u, 1)) & hcon;
       }
@@ -1100,8 +1136,19 @@ __device__ __forceinline__ void crc_packed_body(const RowsArgs& a, std::uint32_t
     if (last) {
       const std::uint32_t slot = k & 63u;
       keep = lane == slot ? (Bn ^ a.out_xor) : keep;
-      if (slot == 63u || k + 1 == nb) {
-        if (lane <= slot) a.out[b0 + k - slot + lane] = keep;
+      if (slot == 63u && k + 1 != nb) {  // (the wave's last register is stored after the row loop)
+        if (!R1 || nheld + 1 >= win) {
+          // the window is full: its oldest register goes out
+          const std::uint32_t oldest = nheld == 0 ? keep : nheld == 1 ? held1 : nheld == 2 ? held2 : held3;
+          store64(k - 63u - 64u * nheld, 63u, oldest);
+        } else {
+          ++nheld;
+        }
+        if constexpr (R1) {
+          held3 = held2;
+          held2 = held1;
+          held1 = keep;
+        }
       }
       r = 0;
       ++k;
@@ -1188,6 +1235,12 @@ __device__ __forceinline__ void crc_packed_body(const RowsArgs& a, std::uint32_t
       }
     }
   }
+  // what the wave still keeps, after its last row: the register being filled, then the held ones
+  const std::uint32_t kl = nb - 1u, sl = kl & 63u;
+  store64(kl - sl, sl, keep);
+  if (R1 && nheld > 0) store64(kl - sl - 64u, 63u, held1);
+  if (R1 && nheld > 1) store64(kl - sl - 128u, 63u, held2);
+  if (R1 && nheld > 2) store64(kl - sl - 192u, 63u, held3);
 }
 
 

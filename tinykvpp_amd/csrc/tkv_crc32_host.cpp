@@ -28,7 +28,7 @@ namespace tkv {
 // ---- launchers (tkv_crc32_kernels.hip) ---------------------------------------------------------
 hipError_t launch_rows(const RowsArgs& a, bool aligned, bool uniform, unsigned grid, hipStream_t st);
 hipError_t launch_fixup(const RowsArgs& a, hipStream_t st);
-hipError_t launch_packed(const RowsArgs& a, bool fold, unsigned grid, hipStream_t st);
+hipError_t launch_packed(const RowsArgs& a, bool fold, bool chunked, unsigned grid, hipStream_t st);
 std::uint32_t packed_small_group(std::uint32_t len);
 hipError_t launch_packed_small(const RowsArgs& a, unsigned grid, hipStream_t st);
 hipError_t launch_lanes(const RowsArgs& a, unsigned ncu, hipStream_t st);
@@ -441,6 +441,11 @@ RowsArgs base_args(DevCtx* c, StreamScratch* s, int algo) {
 // Whether packed CRC-32 batches take the kernel with the segment fold (tkv_debug_set_packed_fold;
 // default 1).
 std::atomic<int> g_packed_fold{1};
+// Packed batches of 4 KiB blocks (crc_packed<true, ...>): result registers a wave keeps
+// before it stores any (tkv_debug_set_packed_window, 0..4) and whether the waves take the blocks in the
+// chunk-strided order (tkv_debug_set_packed_order).
+std::atomic<int> g_packed_window{4};
+std::atomic<int> g_packed_order{1};
 
 // Uniform batches with len <= lane_max() take crc_lanes: kLaneMax.
 long long lane_max() { return static_cast<long long>(kLaneMax); }
@@ -473,7 +478,9 @@ int run_uniform(DevCtx* c, int algo, const std::uint8_t* d_base, std::uint64_t s
     a.snap_blocks = 1;
     // whole blocks per wave, no seams; the segment fold needs CRC-32's polynomial
     const bool fold = g_packed_fold.load(std::memory_order_relaxed) != 0 && algo_poly(algo) == fold::kFoldPoly;
-    TKV_HIP(launch_packed(a, fold, static_cast<unsigned>(c->ncu), st));
+    a.packed_win = static_cast<std::uint32_t>(g_packed_window.load(std::memory_order_relaxed));
+    const bool chunked = g_packed_order.load(std::memory_order_relaxed) != 0;
+    TKV_HIP(launch_packed(a, fold, chunked, static_cast<unsigned>(c->ncu), st));
     return TKV_OK;
   }
   // (aligned back-to-back 64-byte blocks: crc_packed_small's exact G = 1 kernel is faster, 4477 vs
@@ -1444,5 +1451,19 @@ int tkv_debug_set_stream_groups(int enable) { return tkv::g_stream_groups.exchan
 int tkv_debug_set_one_pass(int enable) { return tkv::g_one_pass.exchange(enable ? 1 : 0); }
 
 int tkv_debug_set_packed_fold(int enable) { return tkv::g_packed_fold.exchange(enable ? 1 : 0); }
+int tkv_debug_set_packed_window(int registers) {
+  return tkv::g_packed_window.exchange(registers < 0 ? 0 : registers > 4 ? 4 : registers);
+}
+int tkv_debug_set_packed_order(int enable) { return tkv::g_packed_order.exchange(enable ? 1 : 0); }
+int tkv_debug_batch_uniform_init_device(const uint8_t* d_base, uint64_t stride, uint64_t len, uint32_t init_raw,
+                                        uint32_t* d_out_final, uint64_t n, void* stream) {
+  using namespace tkv;
+  if (n == 0) return TKV_OK;
+  if (!ptr_ok(d_base) || !ptr_ok(d_out_final)) return fail(TKV_INVALID_ARGUMENT, "null pointer");
+  DevCtx* c = nullptr;
+  if (int rc = get_ctx(&c)) return rc;
+  return run_uniform(c, kAlgoCrc32, d_base, stride, len, nullptr, init_raw, kInit, d_out_final, n,
+                     static_cast<hipStream_t>(stream));
+}
 
 }  // extern "C"

@@ -87,6 +87,7 @@ struct RowsArgs {
   std::uint32_t total_rows;          // uniform only (irregular reads row_scan[nblocks])
   std::uint32_t nwaves;
   std::uint32_t snap_blocks;         // uniform: partition by whole blocks (no seams)
+  std::uint32_t packed_win;          // crc_packed, 4 KiB blocks: result registers kept before any is stored (0..4)
   // irregular batches after the prepass split: `offsets`/`lengths` then list the
   // large blocks only (compacted), out_idx maps a compacted block to its batch index, and the small
   // blocks (len <= kSmallMax) are listed in s_off/s_len/s_idx for the small-block phase.

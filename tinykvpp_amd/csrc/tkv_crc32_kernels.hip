@@ -169,11 +169,19 @@ constexpr int kPackedPrio = 3;  // set_prio_from_left thresholds 1/4, 1/8, 1/16
 
 // FOLD (CRC-32 tables only; launch_packed): the lanes fold 24 of their 64 bytes away with shifts and
 // XORs before the table steps (tkv_crc32_fold.h).
-template <bool R1, bool FOLD>
+// CHUNK (4 KiB blocks only; launch_packed): chunk-strided block order (crc_packed_body).
+constexpr int kPackedChunk = 16;
+// Rows in flight / interleaved for 4 KiB blocks (probe builds override them: tools/build_at.sh WT NAME -D...)
+#ifndef TKV_PACKED_R1_DEPTH
+#define TKV_PACKED_R1_DEPTH kPackedDepth
+#define TKV_PACKED_R1_ILP kPackedIlp
+#endif
+template <bool R1, bool FOLD, int CHUNK = 0>
 __global__ __launch_bounds__(kThreads) void crc_packed(RowsArgs a) {
   static_assert(kThreads == 1024, "the skewed partition assumes 16 waves per workgroup");
   __shared__ std::uint32_t lds[kLdsWords];
-  dev::crc_packed_body<kPackedDepth, kPackedIlp, R1, R1 ? 0 : kPackedSkew, kPackedPrio, FOLD>(a, lds);
+  dev::crc_packed_body<R1 ? TKV_PACKED_R1_DEPTH : kPackedDepth, R1 ? TKV_PACKED_R1_ILP : kPackedIlp, R1,
+                       R1 ? 0 : kPackedSkew, kPackedPrio, FOLD, CHUNK>(a, lds);
 }
 
 // Packed small blocks (len = 64 G <= 2 KiB for a power of two G, stride == len, 16-byte aligned,
@@ -1404,10 +1412,17 @@ hipError_t launch_rows(const RowsArgs& a, bool aligned, bool uniform, unsigned g
 }
 
 // fold: the caller's tables are CRC-32's (0xEDB88320) and the segment fold is switched on
-hipError_t launch_packed(const RowsArgs& a, bool fold, unsigned grid, hipStream_t st) {
+// chunked: 4 KiB blocks in the chunk-strided order (chunks of kPackedChunk blocks); blocks of several
+// rows keep their skewed contiguous split
+hipError_t launch_packed(const RowsArgs& a, bool fold, bool chunked, unsigned grid, hipStream_t st) {
   if (a.len == kRow) {
-    if (fold) hipLaunchKernelGGL((crc_packed<true, true>), dim3(grid), dim3(kThreads), 0, st, a);
-    else hipLaunchKernelGGL((crc_packed<true, false>), dim3(grid), dim3(kThreads), 0, st, a);
+    if (fold) {
+      if (chunked) hipLaunchKernelGGL((crc_packed<true, true, kPackedChunk>), dim3(grid), dim3(kThreads), 0, st, a);
+      else hipLaunchKernelGGL((crc_packed<true, true>), dim3(grid), dim3(kThreads), 0, st, a);
+    } else {
+      if (chunked) hipLaunchKernelGGL((crc_packed<true, false, kPackedChunk>), dim3(grid), dim3(kThreads), 0, st, a);
+      else hipLaunchKernelGGL((crc_packed<true, false>), dim3(grid), dim3(kThreads), 0, st, a);
+    }
   } else {
     if (fold) hipLaunchKernelGGL((crc_packed<false, true>), dim3(grid), dim3(kThreads), 0, st, a);
     else hipLaunchKernelGGL((crc_packed<false, false>), dim3(grid), dim3(kThreads), 0, st, a);

@@ -847,6 +847,7 @@ const V kVariants[] = {
     {"pat seg64 D4 fin2 strided", P<0, 4, 2, 0, 1>}, {"stream T1024 ncu", nullptr},
     {"pat seg64 D4 fin2 mis0", P<0, 4, 2, 0>}, {"pat seg64 D4 fin2 mis4", P<0, 4, 2, 4>},
     {"pat seg64 D4 fin2 mis5", P<0, 4, 2, 5>}, {"pat seg64 D4 fin2 mis8", P<0, 4, 2, 8>},
+    {"pat seg64 D2 fin2", P<0, 2, 2>}, {"pat seg64 D2 fin0 strided", P<0, 2, 0, 0, 1>},
     {"pat seg64 D2 fin0", P<0, 2, 0>}, {"pat seg64 D4 fin0", P<0, 4, 0>}, {"pat seg64 D4 fin1", P<0, 4, 1>},
     {"pat seg64 D4 fin2", P<0, 4, 2>}, {"pat coal D2 fin0", P<1, 2, 0>}, {"pat coal D4 fin0", P<1, 4, 0>},
     {"pat coal D4 fin1", P<1, 4, 1>}, {"pat coal D4 fin2", P<1, 4, 2>}, {"pat seg32 D4 fin0", P<2, 4, 0>},
@@ -898,7 +899,8 @@ hipError_t launch_prepass(const std::uint8_t* base, const std::uint64_t* offsets
                           std::uint32_t n, std::uint64_t* scan, std::uint64_t* tile_sums, std::uint32_t* tile_ok,
                           std::uint32_t* counts, std::uint64_t* sinfo, std::uint64_t* ends, const PrepassOut& o,
                           std::uint32_t W, std::uint32_t ncu, std::uint32_t* out, std::uint32_t* row0,
-                          hipStream_t st);
+                          std::uint32_t group_stream, const std::uint32_t* gate, std::uint32_t seq,
+                          const std::uint32_t* gate_flags, hipStream_t st);
 }  // namespace tkv
 
 extern "C" int explore_count() { return kNV + 1; }
@@ -1017,7 +1019,7 @@ extern "C" int explore_run_irr(int v, const std::uint8_t* base, const std::uint6
   // batches with gaps between blocks.
   launch_prepass(base, off, len, a.nblocks, g_scan64, g_tiles64, g_tile_ok, g_counts,
                  reinterpret_cast<std::uint64_t*>(g_counts + 4), g_po.big_off, g_po, a.nwaves, g_ncu, out,
-                 reinterpret_cast<std::uint32_t*>(g_seams) + 16 * g_ncu, st);
+                 reinterpret_cast<std::uint32_t*>(g_seams) + 16 * g_ncu, 0u, nullptr, 0u, nullptr, st);
   kIrr[v].launch(a, st);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
