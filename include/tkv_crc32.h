@@ -665,6 +665,103 @@ int tkv_sst_merge(uint32_t n_runs,
                   uint64_t entry_cap,
                   uint64_t *n_entries, uint64_t *keys_bytes, uint64_t *vals_bytes, uint64_t *first_bad);
 
+/* ---- SSTable get: batched point lookup over sorted runs, newest wins --------------- */
+
+#define TKV_SST_GET_ABSENT  0u   /* no run holds the user key */
+#define TKV_SST_GET_FOUND   1u   /* the newest entry of the key is live */
+#define TKV_SST_GET_DELETED 2u   /* the newest entry of the key is a tombstone */
+
+/* engine::get for a batch: nq user keys looked up in n_runs sorted runs of internal keys, the memtable runs
+ * behind the segments' (engine.cpp:91-121 walks the memtables, then segments_; segment::get_kv_entry does
+ * not compile in the reference, so the read contract is fixed here).
+ * The per-run arguments (d_keys, keys_size, d_key_off, d_key_len, d_val_off, d_val_len, n, d_vals,
+ * vals_size, val_bias) are tkv_sst_merge_device's, with the same meaning: HOST arrays of n_runs elements
+ * whose pointer elements are device pointers (host pointers for tkv_sst_get), runs OLDEST FIRST, n_runs <=
+ * TKV_SST_MERGE_MAX_RUNS, d_val_off / d_val_len NULL as a whole or per run (every value of that run is
+ * empty). d_vals[r] / vals_size[r] name run r's value arena: val_off_r counts from d_vals[r].
+ * Queries: user key j is [d_qkeys + q_off[j], + q_len[j]). The user key of an entry is its internal key
+ * without the last 17 bytes; order is the replay's (unsigned bytes, a prefix first).
+ * Lookup rule: for query j the runs are visited from the HIGHEST-NUMBERED one down. In a run the hit is the
+ * entry with the highest index whose user key equals the query (the upper bound minus one). The first run
+ * with a hit decides: TKV_SST_GET_FOUND when the hit's last key byte is 0, else TKV_SST_GET_DELETED; older
+ * runs are not consulted (engine.cpp:110-118 stops at a tombstone). No hit anywhere: TKV_SST_GET_ABSENT.
+ * Sequence and timestamp take no part. The answer is the one a lookup in tkv_sst_merge_device's output
+ * without the drop flag gives.
+ * Per-query outputs, each nullable and then skipped: state[j]; src[j] = r << 32 | i of the hit,
+ * TKV_SST_MERGE_NONE when ABSENT; seq[j] = the u64 behind the hit's user key, 0 when ABSENT;
+ * out_val_off[j] = val_bias[r] + val_off_r[i] (val_bias NULL: zeros) and out_val_len[j] = val_len_r[i] for
+ * FOUND, (0, 0) otherwise: a DELETED hit reports no value, whatever the entry carries. *n_found = the
+ * count of FOUND.
+ * Value gather: d_vals non-NULL switches it on. The values of the FOUND queries are copied back to back, in
+ * query order, into d_out_vals; out_val_pos[j] = the exclusive u64 prefix sum of out_val_len; *vals_bytes
+ * = the total, reported without the gather too. *vals_bytes > vals_cap with d_out_vals non-NULL:
+ * TKV_BUFFER_OVERFLOW with the two sizes set and nothing written (all outputs NULL and vals_cap 0 is the
+ * sizing call, TKV_OK). Many queries may hit one entry: its value is copied once per query. d_out_vals may
+ * have any byte alignment; nothing outside [d_out_vals, + *vals_bytes) is written or read-modify-written.
+ * THE RUNS ARE NOT VALIDATED AS A WHOLE (a pass over N entries per call would defeat the purpose): they
+ * must be ascending, as the scan, the replay and the merge return them; on a run that is not, the answers
+ * are unspecified but the call stays memory-safe. The search of a run of n entries is fixed: pos = 0; for
+ * step = 2^(b - 1), ..., 2, 1 with b = ceil(log2(n + 1)): entry pos + step - 1 is probed when pos + step
+ * <= n, and pos += step when its user key is <= the query; the hit is entry pos - 1 when the last probe
+ * that advanced pos compared equal. Every probed entry is span-checked before its key is read (key_len >=
+ * 17, key_len < 2^28, key_off + key_len <= keys_size[r]); with the gather on, a FOUND hit's val_off +
+ * val_len <= vals_size[r] is checked too (a NULL d_vals[r] counts as an arena of 0 bytes). A query stops at
+ * its first failed check. Any failed check: TKV_CORRUPTED, *first_bad = the smallest r << 32 | i among the
+ * entries that were read and failed (the probe sequence is the one above in both calls, so this is
+ * deterministic), the two sizes 0, no output array written. An entry no search reads is not checked.
+ * Otherwise *first_bad = TKV_SST_MERGE_NONE.
+ * Bad queries: q_off[j] + q_len[j] > qkeys_size or q_len[j] + 17 >= 2^28 for some j: TKV_INVALID_ARGUMENT,
+ * found by the first pass (on the device in the device call), no output touched. It goes before
+ * TKV_CORRUPTED.
+ * TKV_INVALID_ARGUMENT, before any device work and with nothing touched: the merge's errors for the run
+ * arguments (n_runs > TKV_SST_MERGE_MAX_RUNS; with n_runs > 0 NULL d_keys / keys_size / d_key_off /
+ * d_key_len / n, or a NULL element of d_keys / d_key_off / d_key_len for a run with n[r] > 0; d_val_len[r]
+ * without d_val_off[r]; some n[r] > 2^32 - 1 or the total N > 2^32 - 1); flags != 0; NULL n_found /
+ * vals_bytes / first_bad; with nq > 0 NULL d_q_off / d_q_len, or NULL d_qkeys with qkeys_size > 0; nq >
+ * 2^32 - 1; d_vals without vals_size; d_out_vals or d_out_val_pos without d_vals.
+ * nq == 0: TKV_OK, sizes 0, *first_bad = TKV_SST_MERGE_NONE, nothing else touched. n_runs == 0 or every
+ * run empty: every query is ABSENT.
+ * Reads: no byte outside a run's [d_keys[r], + keys_size[r]) or [d_qkeys, + qkeys_size) is read, beyond the
+ * aligned 16-byte granule that holds a key byte (the replay's rule); values are read only by the gather,
+ * and only inside [d_vals[r], + vals_size[r]) under the same rule.
+ * The device call is synchronous on `stream` with at most TWO host synchronisations: one for the verdicts
+ * and the sizes (the kernels behind the search read the verdicts on the device and write nothing when one
+ * is set), one at the end of the emit. With no usable GPU it returns TKV_IO_ERROR; a scratch allocation
+ * that fails returns TKV_OUT_OF_MEMORY (the scratch holds 32 bytes per query: the hit, state and value
+ * length, and the two scans; plus 16 bytes per 1024 queries for the scans' sums, 8 per 4096 gathered bytes
+ * for the emit's tile table and 96 per run). No key byte crosses PCIe: only the run table and a small
+ * pinned result block do. One GPU. */
+int tkv_sst_get_device(uint32_t n_runs,
+                       const uint8_t *const *d_keys, const uint64_t *keys_size,
+                       const uint64_t *const *d_key_off, const uint32_t *const *d_key_len,
+                       const uint64_t *const *d_val_off, const uint32_t *const *d_val_len,
+                       const uint64_t *n,
+                       const uint8_t *const *d_vals, const uint64_t *vals_size,   /* nullable: no gather */
+                       const uint64_t *val_bias,
+                       const uint8_t *d_qkeys, uint64_t qkeys_size,
+                       const uint64_t *d_q_off, const uint32_t *d_q_len, uint64_t nq, uint32_t flags,
+                       uint8_t *d_state, uint64_t *d_src, uint64_t *d_seq,
+                       uint64_t *d_out_val_off, uint32_t *d_out_val_len,
+                       uint64_t *d_out_val_pos, uint8_t *d_out_vals, uint64_t vals_cap,
+                       uint64_t *n_found, uint64_t *vals_bytes, uint64_t *first_bad, void *stream);
+
+/* The same contract with every pointer in HOST memory: the queries split over host threads, the same
+ * search with a full-key comparator, the same checks on probed entries only, the same verdict precedence
+ * and outputs. It uses no GPU at all and is NOT a fallback of the device call. */
+int tkv_sst_get(uint32_t n_runs,
+                const uint8_t *const *h_keys, const uint64_t *keys_size,
+                const uint64_t *const *h_key_off, const uint32_t *const *h_key_len,
+                const uint64_t *const *h_val_off, const uint32_t *const *h_val_len,
+                const uint64_t *n,
+                const uint8_t *const *h_vals, const uint64_t *vals_size,
+                const uint64_t *val_bias,
+                const uint8_t *h_qkeys, uint64_t qkeys_size,
+                const uint64_t *h_q_off, const uint32_t *h_q_len, uint64_t nq, uint32_t flags,
+                uint8_t *h_state, uint64_t *h_src, uint64_t *h_seq,
+                uint64_t *h_out_val_off, uint32_t *h_out_val_len,
+                uint64_t *h_out_val_pos, uint8_t *h_out_vals, uint64_t vals_cap,
+                uint64_t *n_found, uint64_t *vals_bytes, uint64_t *first_bad);
+
 /* ---- CRC-32C (Castagnoli) — SURVEY.md §8f rank 4 ------------------------------------------------ */
 
 /* Same engine and kernels with the tables of the Castagnoli polynomial (reflected 0x82F63B78,
@@ -934,6 +1031,19 @@ void tkv_debug_sst_merge_last(uint64_t out[4]);
  * merge rounds, out_ms[2] = ties, tombstone drop and the survivor scan, out_ms[3] = emit (with the host's
  * read of the verdict and the sizes in front). Switch and return value as tkv_debug_sst_build_phases. */
 int tkv_debug_sst_merge_phases(int enable, double out_ms[4]);
+
+/* Geometry of tkv_sst_get_device: out[0] = queries per workgroup of the search (one lane per query).
+ * Tests place their query counts around it. */
+void tkv_debug_sst_get_geometry(uint64_t out[1]);
+/* What the calling thread's last tkv_sst_get_device did: out[0] = nq, out[1] = n_runs, out[2] = the search
+ * steps of the lane that made the most (the sum of ceil(log2(n[r] + 1)) over the runs that lane searched),
+ * out[3] = queries FOUND, out[4] = queries DELETED (all 0 when it did not reach its end). */
+void tkv_debug_sst_get_last(uint64_t out[5]);
+/* Phase times of the calling thread's last tkv_sst_get_device that returned TKV_OK, in milliseconds
+ * between device events on its stream: out_ms[0] = the search, out_ms[1] = the two scans, out_ms[2] = the
+ * per-query columns and the tile table (with the host's read of the verdicts and the sizes in front),
+ * out_ms[3] = the value gather. Switch and return value as tkv_debug_sst_build_phases. */
+int tkv_debug_sst_get_phases(int enable, double out_ms[4]);
 
 #ifdef __cplusplus
 }

@@ -25,5 +25,5 @@ from .crc32 import (  # noqa: F401
 )
 from . import memtable, sst, wal  # noqa: F401
 from .memtable import MemtableRun  # noqa: F401
-from .sst import MergeCorrupted, MergedRun  # noqa: F401
+from .sst import GetCorrupted, GetResult, MergeCorrupted, MergedRun  # noqa: F401
 from .wal import WalBatch, resync_device, salvage, salvage_device  # noqa: F401

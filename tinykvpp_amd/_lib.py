@@ -107,6 +107,12 @@ SIGNATURES = {
     "tkv_debug_sst_merge_tile": (_u64, []),
     "tkv_debug_sst_merge_last": (None, [_vp]),
     "tkv_debug_sst_merge_phases": (_int, [_int, _vp]),
+    "tkv_sst_get_device": (_int, [_u32] + [_vp] * 11 + [_u64, _vp, _vp, _u64, _u32] + [_vp] * 7 + [_u64] +
+                           [ctypes.POINTER(_u64)] * 3 + [_vp]),
+    "tkv_sst_get": (_int, [_u32] + [_vp] * 11 + [_u64, _vp, _vp, _u64, _u32] + [_vp] * 7 + [_u64] + [ctypes.POINTER(_u64)] * 3),
+    "tkv_debug_sst_get_geometry": (None, [_vp]),
+    "tkv_debug_sst_get_last": (None, [_vp]),
+    "tkv_debug_sst_get_phases": (_int, [_int, _vp]),
     "tkv_crc32c_update": (_int, [_u32, _vp, _sz, ctypes.POINTER(_u32)]),
     "tkv_crc32c_update_device": (_int, [_u32, _vp, _sz, _vp, _vp]),
     "tkv_crc32c_batch_device": (_int, [_u8p, _vp, _vp, _vp, _vp, _u64, _vp]),
@@ -163,7 +169,8 @@ OPTIONAL = {"tkv_build_id", "tkv_wal_index_device", "tkv_wal_index", "tkv_debug_
             "tkv_debug_sst_scan_geometry", "tkv_debug_sst_scan_last", "tkv_debug_sst_scan_phases",
             "tkv_memtable_build_device", "tkv_memtable_build", "tkv_debug_memtable_geom", "tkv_debug_memtable_last",
             "tkv_debug_memtable_phases", "tkv_debug_memtable_passes", "tkv_sst_merge_device", "tkv_sst_merge",
-            "tkv_debug_sst_merge_tile", "tkv_debug_sst_merge_last", "tkv_debug_sst_merge_phases"}
+            "tkv_debug_sst_merge_tile", "tkv_debug_sst_merge_last", "tkv_debug_sst_merge_phases", "tkv_sst_get_device",
+            "tkv_sst_get", "tkv_debug_sst_get_geometry", "tkv_debug_sst_get_last", "tkv_debug_sst_get_phases"}
 
 _lib = None
 

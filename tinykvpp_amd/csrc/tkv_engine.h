@@ -219,4 +219,42 @@ struct SstMergeCall {
 // 1 <= N <= 2^32 - 1 by the caller).
 int sst_merge_device_impl(const SstMergeCall& c, hipStream_t st);
 
+// The arguments of tkv_sst_get[_device] (include/tkv_crc32.h "SSTable get"): the per-run arrays are host
+// arrays of n_runs elements in both calls, as the merge's.
+struct SstGetCall {
+  std::uint32_t n_runs;
+  const std::uint8_t* const* keys;
+  const std::uint64_t* keys_size;
+  const std::uint64_t* const* key_off;
+  const std::uint32_t* const* key_len;
+  const std::uint64_t* const* val_off;  // nullable, and every element nullable
+  const std::uint32_t* const* val_len;
+  const std::uint64_t* n;
+  const std::uint8_t* const* vals;  // nullable: no gather, no value span check
+  const std::uint64_t* vals_size;
+  const std::uint64_t* val_bias;    // nullable: zeros
+  const std::uint8_t* qkeys;
+  std::uint64_t qkeys_size;
+  const std::uint64_t* q_off;
+  const std::uint32_t* q_len;
+  std::uint64_t nq;
+  std::uint32_t flags;
+  std::uint8_t* state;
+  std::uint64_t* src;
+  std::uint64_t* seq;
+  std::uint64_t* out_val_off;
+  std::uint32_t* out_val_len;
+  std::uint64_t* out_val_pos;
+  std::uint8_t* out_vals;
+  std::uint64_t vals_cap;
+  std::uint64_t *n_found, *vals_bytes, *first_bad;
+};
+
+// tkv_sst_get.hip: the batched point lookup on `st` (synchronous): the query check and the per-run
+// upper-bound searches of one lane per query, the scans of the found flags and the value lengths, the
+// host's invalid / corrupted / overflow decision from a pinned result, the columns and the value gather.
+// Arguments and results are tkv_sst_get_device's (the argument checks made and 1 <= nq <= 2^32 - 1 by the
+// caller).
+int sst_get_device_impl(const SstGetCall& c, hipStream_t st);
+
 }  // namespace tkv

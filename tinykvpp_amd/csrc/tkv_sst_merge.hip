@@ -40,6 +40,7 @@
 #include "tkv_engine.h"
 #include "tkv_key_word.h"
 #include "tkv_memtable_layout.h"
+#include "tkv_runs_device.h"
 #include "tkv_scan.h"
 
 namespace tkv {
@@ -49,23 +50,7 @@ constexpr unsigned kMgThreads = 256;
 constexpr unsigned kMgItems = 8;                               // outputs a thread merges serially
 constexpr std::uint32_t kMgTile = kMgThreads * kMgItems;       // outputs per workgroup: 32 KiB of LDS
 constexpr unsigned kMgHres = 8;                                // words of the pinned result block
-constexpr unsigned kMgDigitShift = 40, kMgRunShift = 32;       // the sort entry's second word
-constexpr std::uint64_t kMgIdxMask = 0xFFFFFFFFull;
 enum : int { kMsBad = 0, kMsKeys, kMsVals, kMsWords };
-static_assert(TKV_SST_MERGE_MAX_RUNS <= 256, "the run takes 8 bits of the sort entry");
-
-// One run as the kernels see it.
-struct MgRun {
-  const std::uint8_t* keys;
-  std::uint64_t keys_size;
-  const std::uint64_t* key_off;
-  const std::uint32_t* key_len;
-  const std::uint64_t* val_off;  // nullable
-  const std::uint32_t* val_len;  // nullable
-  std::uint64_t start;           // entries of the runs before it
-  std::uint64_t key_bias;        // keys - key_base
-  std::uint64_t val_bias;
-};
 
 // A workgroup's share of a round: the pair's lists in[s0, s1) and in[s1, s2), outputs [d, d + kMgTile) of
 // out[s0, s2).
@@ -96,41 +81,6 @@ struct MgArgs {
   std::uint64_t* o_src;
 };
 
-struct MgKey {
-  std::uintptr_t addr;
-  std::uint32_t ulen;
-};
-
-__device__ __forceinline__ const MgRun& run_of(const MgRun* runs, std::uint64_t x) { return runs[(x >> kMgRunShift) & 0xFFu]; }
-
-// The user key of a checked entry.
-__device__ __forceinline__ MgKey key_of(const MgRun* runs, std::uint64_t x) {
-  const MgRun& r = run_of(runs, x);
-  const std::uint64_t i = x & kMgIdxMask;
-  return MgKey{reinterpret_cast<std::uintptr_t>(r.keys) + r.key_off[i], r.key_len[i] - kMtMeta};
-}
-
-// Two keys equal in their first 8 bytes and both longer: their order by the words behind.
-__device__ int cmp_rest(MgKey a, MgKey b) {
-  for (std::uint32_t o = kMtWordBytes;; o += kMtWordBytes) {
-    const std::uint64_t ra = a.ulen - o, rb = b.ulen - o;  // >= 1: the digit in front said the key goes on
-    const std::uint64_t wa = load_word(a.addr + o, ra), wb = load_word(b.addr + o, rb);
-    if (wa != wb) return wa < wb ? -1 : 1;
-    const std::uint32_t da = mt_digit(ra), db = mt_digit(rb);
-    if (da != db) return da < db ? -1 : 1;
-    if (da < kMtDigitMore) return 0;
-  }
-}
-
-// The one comparator of the check, the partition search, the tile merge and the ties.
-__device__ __forceinline__ int mg_cmp(const MgRun* runs, std::uint64_t wa, std::uint64_t xa, std::uint64_t wb, std::uint64_t xb) {
-  if (wa != wb) return wa < wb ? -1 : 1;
-  const std::uint32_t da = static_cast<std::uint32_t>(xa >> kMgDigitShift), db = static_cast<std::uint32_t>(xb >> kMgDigitShift);
-  if (da != db) return da < db ? -1 : 1;
-  if (da < kMtDigitMore) return 0;
-  return cmp_rest(key_of(runs, xa), key_of(runs, xb));
-}
-
 __device__ __forceinline__ bool verdict_bad(const unsigned long long* st) {
   return __hip_atomic_load(st + kMsBad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ull;
 }
@@ -141,10 +91,6 @@ __global__ void mg_init(unsigned long long* st) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     st[kMsBad] = ~0ull;
   }
-}
-
-__device__ __forceinline__ bool span_ok(const MgRun& r, std::uint64_t ko, std::uint32_t kl) {
-  return kl >= kMtMeta && kl < kMtMaxIkey && ko <= r.keys_size && kl <= r.keys_size - ko;
 }
 
 __global__ __launch_bounds__(kScanThreads) void mg_check(MgArgs a, MgList l) {
@@ -372,24 +318,8 @@ __global__ __launch_bounds__(kScanThreads) void mg_emit(MgArgs a, MgList l) {
 // Per-device scratch, grown by doubling and kept between calls (guarded by mu).
 struct MgScratch : ScratchBase {
   DeviceBuf w[2], x[2], scan, sums, bytes, live, runs, tiles;
-  // pinned staging of the run table and the tile map (the copies to the device are asynchronous)
-  void* h_stage = nullptr;
-  std::uint64_t h_cap = 0;
+  RunStage hs;  // pinned staging of the run table and the tile map
   unsigned long long*& st = words;
-  ~MgScratch() { (void)hipHostFree(h_stage); }
-  int stage(std::uint64_t bytes) {
-    if (bytes <= h_cap) return TKV_OK;
-    const std::uint64_t c = std::max<std::uint64_t>(bytes, 2 * h_cap);
-    (void)hipHostFree(h_stage);
-    h_stage = nullptr;
-    h_cap = 0;
-    if (hipHostMalloc(&h_stage, c, hipHostMallocDefault) != hipSuccess) {
-      h_stage = nullptr;
-      return set_error(TKV_OUT_OF_MEMORY, "sst merge: pinned staging allocation failed");
-    }
-    h_cap = c;
-    return TKV_OK;
-  }
 };
 
 // The calling thread's device merges (tkv_debug_sst_merge_last, tkv_debug_sst_merge_phases).
@@ -457,11 +387,11 @@ int merge_locked(MgScratch& s, const SstMergeCall& c, hipStream_t st) {
   if (int rc = take(s.runs, K, &d_runs)) return rc;
   if (int rc = take(s.tiles, std::max<std::uint64_t>(tiles.size(), 1), &d_tiles)) return rc;
   const std::uint64_t rbytes = K * sizeof(MgRun), tbytes = tiles.size() * sizeof(MgTile);
-  if (int rc = s.stage(rbytes + tbytes)) return rc;
-  std::memcpy(s.h_stage, runs.data(), rbytes);
-  if (tbytes) std::memcpy(static_cast<std::uint8_t*>(s.h_stage) + rbytes, tiles.data(), tbytes);
-  TKV_HIP_RC(hipMemcpyAsync(d_runs, s.h_stage, rbytes, hipMemcpyHostToDevice, st));
-  if (tbytes) TKV_HIP_RC(hipMemcpyAsync(d_tiles, static_cast<std::uint8_t*>(s.h_stage) + rbytes, tbytes, hipMemcpyHostToDevice, st));
+  if (int rc = s.hs.stage(rbytes + tbytes, "sst merge: pinned staging allocation failed")) return rc;
+  std::memcpy(s.hs.h, runs.data(), rbytes);
+  if (tbytes) std::memcpy(static_cast<std::uint8_t*>(s.hs.h) + rbytes, tiles.data(), tbytes);
+  TKV_HIP_RC(hipMemcpyAsync(d_runs, s.hs.h, rbytes, hipMemcpyHostToDevice, st));
+  if (tbytes) TKV_HIP_RC(hipMemcpyAsync(d_tiles, static_cast<std::uint8_t*>(s.hs.h) + rbytes, tbytes, hipMemcpyHostToDevice, st));
   a.runs = d_runs;
   a.n_runs = K;
   a.flags = c.flags;

@@ -445,10 +445,11 @@ class MergedRun:
     """What merge_device / merge return: one entry per surviving user key, ascending. ``key_off`` /
     ``val_off`` count from the addresses ``key_base`` / ``val_base`` (the lowest key / value arena among the
     runs; ``keys`` / ``vals`` are those arenas), ``key_len`` / ``val_len`` are the entries' own, ``src`` =
-    run << 32 | index names the surviving entry. ``arenas`` keeps every input arena alive."""
+    run << 32 | index names the surviving entry. ``arenas`` keeps every input arena alive; ``key_arenas`` /
+    ``val_arenas`` are its two kinds (the bounds of the offsets for a later get)."""
 
     __slots__ = ("keys", "vals", "key_base", "val_base", "key_off", "key_len", "val_off", "val_len", "src", "n_entries",
-                 "keys_bytes", "vals_bytes", "arenas")
+                 "keys_bytes", "vals_bytes", "arenas", "key_arenas", "val_arenas")
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -546,7 +547,7 @@ def _merge(fn, cols, addr, count, alloc, ptr, drop_tombstones, tail, spare):
     return MergedRun(keys=keys, vals=vals, key_base=key_base, val_base=val_base, key_off=out[0], key_len=out[1],
                      val_off=out[2], val_len=out[3], src=out[4], n_entries=m, keys_bytes=res[1].value,
                      vals_bytes=res[2].value,
-                     arenas=[t for c in cols for t in (c[0], c[3]) if has(t)])
+                     arenas=[t for c in cols for t in (c[0], c[3]) if has(t)], key_arenas=key_arenas, val_arenas=val_arenas)
 
 
 def merge_device(runs, drop_tombstones=False, stream=None):
@@ -619,3 +620,174 @@ def compact(files, target_block_size=4096, drop_tombstones=False):
     """The same through the host calls (scan, merge, build)."""
     runs = [scan(f, key_views=True, val_views=True) for f in files]
     return merge(runs, drop_tombstones=drop_tombstones).flush(target_block_size)
+
+
+# ---- get: batched point lookup over sorted runs, newest wins (include/tkv_crc32.h "SSTable get") ------
+GET_ABSENT, GET_FOUND, GET_DELETED = 0, 1, 2
+
+
+class GetCorrupted(ValueError):
+    """A run the get rejects: entry ``index`` of run ``run`` was read by a search and its key span (or, as a
+    hit, its value span) does not hold."""
+
+    def __init__(self, run, index):
+        self.run, self.index = run, index
+        super().__init__(f"entry {index} of run {run} has a bad key or value span")
+
+
+class GetResult:
+    """What get_device / get return, one element per query: ``state`` (GET_ABSENT / GET_FOUND /
+    GET_DELETED), ``src`` = run << 32 | index of the hit (MERGE_NONE when absent), ``seq`` the hit's
+    sequence, ``val_off`` / ``val_len`` the value span of a found key (``val_off`` counts from the lowest
+    value arena among the runs), and with values ``val_pos`` / ``vals``: the found values back to back in
+    query order, value j at ``vals[val_pos[j]:val_pos[j] + val_len[j]]``. ``n_found`` and ``vals_bytes``
+    are the totals."""
+
+    __slots__ = ("state", "src", "seq", "val_off", "val_len", "val_pos", "vals", "n_found", "vals_bytes")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def items(self):
+        """(state, value-or-None) per query; the value as bytes for a found key when values were gathered."""
+        def host(t, dt):
+            return None if t is None else (t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)).view(dt)
+        state, vl = host(self.state, np.uint8), host(self.val_len, np.uint32)
+        pos, raw = host(self.val_pos, np.uint64), host(self.vals, np.uint8)
+        raw = None if raw is None else raw.tobytes()
+        for j in range(state.size):
+            found = int(state[j]) == GET_FOUND and raw is not None
+            yield int(state[j]), (raw[int(pos[j]):int(pos[j]) + int(vl[j])] if found else None)
+
+
+def _get_columns(run, addr, count):
+    """_run_columns, and also a MergedRun (its offsets count from its bases: the key arena is passed from
+    the key base to the end of the highest input key arena, the value arena likewise over the value arenas,
+    0 bytes when the merge had none) and a dict with the six column names. Returns (columns, keys_size,
+    vals_size)."""
+    if isinstance(run, MergedRun):
+        keys_end = max([addr(t) + count(t) for t in run.key_arenas], default=run.key_base)
+        vals_end = max([addr(t) + count(t) for t in run.val_arenas], default=run.val_base)
+        return (run.keys, run.key_off, run.key_len, run.vals, run.val_off, run.val_len), max(keys_end - run.key_base, 0), \
+            max(vals_end - run.val_base, 0)
+    if isinstance(run, dict):
+        run = tuple(run.get(k) for k in ("keys", "key_off", "key_len", "vals", "val_off", "val_len"))
+    cols = _run_columns(run)
+    return cols, (count(cols[0]) if cols[0] is not None else 0), (count(cols[3]) if cols[3] is not None else 0)
+
+
+def _get(fn, runs, queries, values, addr, count, alloc, ptr, tail):
+    """The sizing call, then the get into freshly allocated columns (``addr`` / ``count`` / ``alloc`` /
+    ``ptr`` as in _merge). ``queries`` = (arena, off, len)."""
+    from ._lib import BUFFER_OVERFLOW
+    K = len(runs)
+    if K > MERGE_MAX_RUNS:
+        raise ValueError(f"{K} runs: a get takes at most {MERGE_MAX_RUNS}")
+    got = [_get_columns(r, addr, count) for r in runs]
+    cols = [g[0] for g in got]
+    n = [count(c[2]) for c in cols]
+
+    def has(t):
+        return t is not None and count(t) > 0
+    val_arenas = [c[3] for c, k in zip(cols, n) if k and has(c[3])]
+    val_base = min(addr(t) for t in val_arenas) if val_arenas else 0
+
+    def table(ctype, vals):
+        return (ctype * max(K, 1))(*vals)
+    vp, u64 = ctypes.c_void_p, ctypes.c_uint64
+    a_keys = table(vp, [addr(c[0]) if has(c[0]) else None for c in cols])
+    a_size = table(u64, [g[1] for g in got])
+    a_koff = table(vp, [addr(c[1]) if has(c[1]) else None for c in cols])
+    a_klen = table(vp, [addr(c[2]) if has(c[2]) else None for c in cols])
+    a_voff = table(vp, [addr(c[4]) if has(c[4]) and has(c[5]) else None for c in cols])
+    a_vlen = table(vp, [addr(c[5]) if has(c[4]) and has(c[5]) else None for c in cols])
+    a_n = table(u64, n)
+    a_vals = table(vp, [addr(c[3]) if has(c[3]) else None for c in cols]) if values else None
+    a_vsize = table(u64, [g[2] if has(c[3]) else 0 for g, c in zip(got, cols)]) if values else None
+    a_bias = table(u64, [addr(c[3]) - val_base if k and has(c[3]) else 0 for c, k in zip(cols, n)])
+    qkeys, q_off, q_len = queries
+    nq = count(q_len)
+    res = [u64(0) for _ in range(3)]  # n_found, vals_bytes, first_bad
+
+    def call(out, cap):
+        rc = fn(K, a_keys, a_size, a_koff, a_klen, a_voff, a_vlen, a_n, a_vals, a_vsize, a_bias, ptr(qkeys), count(qkeys),
+                ptr(q_off), ptr(q_len), nq, 0, *[ptr(t) for t in out], cap, *[ctypes.byref(r) for r in res], *tail)
+        if rc == CORRUPTED:
+            raise GetCorrupted(res[2].value >> 32, res[2].value & 0xFFFFFFFF)
+        return rc
+    rc = call([None] * 7, 0)  # the sizing call
+    if rc not in (OK, BUFFER_OVERFLOW):
+        check(rc)
+    total = res[1].value
+    kinds = ("u8", "u64", "u64", "u64", "u32", "u64", "u8")  # state, src, seq, val_off, val_len, val_pos, vals
+    out = [alloc(total if k == 6 else nq, kind) if values or k < 5 else None for k, kind in enumerate(kinds)]
+    if nq:
+        check(call(out, total))
+    return GetResult(state=out[0], src=out[1], seq=out[2], val_off=out[3], val_len=out[4], val_pos=out[5], vals=out[6],
+                     n_found=res[0].value, vals_bytes=total)
+
+
+def _query_arena(keys):
+    """(arena, off, len) as numpy arrays of a list of bytes."""
+    ln = np.array([len(k) for k in keys], np.uint32)
+    off = np.zeros(len(keys), np.uint64)
+    if len(keys) > 1:
+        off[1:] = np.cumsum(ln[:-1], dtype=np.uint64)
+    return np.frombuffer(b"".join(keys), np.uint8).copy(), off, ln
+
+
+def get_device(runs, keys, values=True, stream=None):
+    """engine::get for a batch on the device (tkv_sst_get_device). ``runs`` is a list, OLDEST FIRST (the
+    memtable runs last), of what merge_device takes, of MergedRuns, or of dicts with the column names
+    ``keys, key_off, key_len, vals, val_off, val_len``. ``keys`` is a list of ``bytes`` (copied to the device
+    once) or an (arena, off, len) triple of CUDA tensors (uint8, int64, int32). For every key the newest run
+    that holds it decides: found, deleted (a tombstone) or absent. With ``values`` the found values are
+    gathered into one arena. Makes the sizing call, then the get. Returns a GetResult of CUDA tensors. A bad
+    entry a search reads raises GetCorrupted. Synchronous on ``stream``."""
+    import torch
+    from .crc32 import _check_vec, _launch_stream
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if isinstance(keys, (list, tuple)) and not (len(keys) == 3 and hasattr(keys[0], "data_ptr")):
+        a, off, ln = _query_arena(list(keys))
+        keys = (torch.from_numpy(a).to(dev), torch.from_numpy(off.view(np.int64)).to(dev), torch.from_numpy(ln.view(np.int32)).to(dev))
+    qkeys, q_off, q_len = keys
+    nq = q_len.numel()
+    _check_vec("keys", qkeys, torch.uint8, 0, q_len.device)
+    _check_vec("key offsets", q_off, torch.int64, nq, q_len.device)
+    _check_vec("key lengths", q_len, torch.int32, nq, q_len.device)
+    dev = q_len.device
+    other = stream is not None and stream != torch.cuda.current_stream(dev)
+    kinds = {"u8": torch.uint8, "u64": torch.int64, "u32": torch.int32}
+
+    def alloc(count, kind):
+        t = torch.empty(count, dtype=kinds[kind], device=dev)
+        if other:
+            t.record_stream(stream)
+        return t
+    return _get(load_library().tkv_sst_get_device, runs, (qkeys, q_off, q_len), values, lambda t: t.data_ptr(),
+                lambda t: t.numel(), alloc, lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None,
+                (_launch_stream(stream, dev),))
+
+
+def get(runs, keys, values=True):
+    """The same on the host (tkv_sst_get: host threads, no GPU): runs of numpy arrays, ``keys`` a list of
+    ``bytes`` or an (arena, off, len) triple of arrays. Returns a GetResult of numpy arrays."""
+    def arr(a, dt):
+        return None if a is None else np.ascontiguousarray(a, dtype=dt)
+    dts = (np.uint8, np.uint64, np.uint32, np.uint8, np.uint64, np.uint32)
+    host = []
+    for run in runs:
+        if isinstance(run, MergedRun):
+            host.append(run)
+            continue
+        if isinstance(run, dict):
+            run = tuple(run.get(k) for k in ("keys", "key_off", "key_len", "vals", "val_off", "val_len"))
+        host.append(tuple(arr(a, dt) for a, dt in zip(_run_columns(run), dts)))
+    if isinstance(keys, (list, tuple)) and not (len(keys) == 3 and isinstance(keys[0], np.ndarray)):
+        keys = _query_arena(list(keys))
+    queries = tuple(arr(a, dt) for a, dt in zip(keys, dts[:3]))
+    kinds = {"u8": np.uint8, "u64": np.uint64, "u32": np.uint32}
+    return _get(load_library().tkv_sst_get, host, queries, values, lambda a: a.ctypes.data, lambda a: a.size,
+                lambda count, kind: np.empty(count, kinds[kind]),
+                lambda a: ctypes.c_void_p(a.ctypes.data) if a is not None and a.size else None, ())
